@@ -3,7 +3,12 @@
 observation points, plus the achieved fraction of the HBM roofline for the kernel and the CPU
 oracle timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the record line.
+`--dump-outputs DIR` writes what the last timed step computed (see `dump_index`).  Everything else
+the record can carry (the N = 1 blocks listed below, and at N > 1 the cfg5 block and the single-GPU
+figure) is measured only with `--full`.
 
 * The headline (`value`, `roofline`) is BASELINE.json configs[1] at every N: 3-D multilinear-regular,
   64^3 f64 grid, 1e8 random obs PER GPU (weak scaling over a fixed grid, as north_star asks), so
@@ -20,8 +25,9 @@ oracle timed beside it.
 A step is one pass of the hot path over one batch: one `interpn_hip_eval_device` launch over the
 rank's device-resident points followed by the status check (`interpn_hip_finish`).  Inputs are
 synthetic: axes linspace(-1,1,n), vals U(-1,1), obs i.i.d. uniform over the
-grid extent, unordered.  EXACTLY K steps are timed between barrier + synchronize pairs; rank 0
-prints ONE JSON line.  At N = 1 the line also carries
+grid extent, unordered, all from fixed seeds.  EXACTLY K steps are timed between barrier + synchronize
+pairs; rank 0 prints ONE JSON line.  At N = 1 with `--full` the line also carries
+  roofline.measured_copy_GBps  a device-to-device copy of one coordinate array, for scale,
   roofline.sustained   the same launch repeated for >= 0.5 s (K may be as small as 20 = 26 ms),
   roofline.ablation    stream-only / gather-only variants of the same kernel source (the L2-bound
                        ceiling argument of DESIGN.md section 4.1, reproducible by the driver),
@@ -29,7 +35,8 @@ prints ONE JSON line.  At N = 1 the line also carries
                        linearize flags, the cfg5 shard): kernel time, roofline fraction, the kernel
                        name queried from the handle, and a bitwise check of sampled points against
                        the CPU oracle (outside every timed region),
-  cpu_baseline         the oracle (a port: the Rust reference cannot be built here) on host cores.
+  cpu_baseline         the oracle (a port: the Rust reference cannot be built here) on host cores,
+  roofline.brick_kernel / coherent_batch / traffic_live, host_path.
 """
 
 from __future__ import annotations
@@ -65,6 +72,12 @@ def parse(argv=None):
                     help="headline grid: auto = cfg2 (64^3) at every N; cfg5 = 128^3")
     ap.add_argument("--points", type=int, default=100_000_000, help="observation points per GPU")
     ap.add_argument("--grid", type=int, default=0, help="grid points per axis (0 = the workload's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (float64; see dump_index)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: CPU baseline, configurations, ablations, "
+                         "live traffic, host path (N = 1); the cfg5 block and the single-GPU figure (N > 1)")
+    # The --no-* options below and --cpu-sample / --sustain-seconds shape the measurements of --full.
     ap.add_argument("--cpu-sample", type=int, default=0, help="points for the CPU baseline (0 = auto, ~10-20 s)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the per-configuration table (N = 1)")
@@ -85,7 +98,10 @@ def parse(argv=None):
     # CPU test of the spawn / rendezvous path only (tests/test_bench_spawn.py): no GPU work, every
     # rank joins a gloo group and rank 0 prints who took part.  Not a benchmark.
     ap.add_argument("--dry-run", action="store_true")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -211,6 +227,29 @@ def build_spec(method, kind, n, ndims, linearize, seed):
     return {"method": method, "kind": kind, "n": n, "ndims": ndims, "linearize": bool(linearize),
             "dims": [n] * ndims, "starts": np.full(ndims, -1.0), "steps": np.full(ndims, step), "grids": grids,
             "vals": rng.uniform(-1.0, 1.0, n**ndims)}
+
+
+def make_obs(torch, dev, P, rank, ndims=3):
+    """A rank's observation shard: i.i.d. uniform over the grid extent, device resident, the same bits on every run."""
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(3 + 1000 * rank)
+    return [torch.rand(P, dtype=torch.float64, device=dev, generator=gen) * 2.0 - 1.0 for _ in range(ndims)], gen
+
+
+DUMP_POINTS = 4_000_000  # results written by --dump-outputs over all ranks: 32 MB of f64
+
+
+def dump_index(P, rank, world):
+    """Indices into a rank's output that --dump-outputs writes: the whole output if it is small enough, else a fixed,
+    seeded, sorted sample (with repeats) of DUMP_POINTS // world of them."""
+    m = DUMP_POINTS // world
+    if P <= m:
+        return np.arange(P, dtype=np.int64)
+    return np.sort(np.random.default_rng(7 + 1000 * rank).integers(0, P, m, dtype=np.int64))
+
+
+def dump_name(rank):
+    return "out.npy" if rank == 0 else f"out_rank{rank}.npy"
 
 
 def make_interp(interpn_amd, spec, device, vals=None):
@@ -893,15 +932,14 @@ def worker(args):
             dist.barrier()
 
     # Observation shard of this rank: i.i.d. uniform over the grid extent, device resident.
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(3 + 1000 * rank)
-    obs = [torch.rand(P, dtype=torch.float64, device=dev, generator=gen) * 2.0 - 1.0 for _ in range(NDIMS)]
+    obs, gen = make_obs(torch, dev, P, rank, NDIMS)
     out = torch.empty(P, dtype=torch.float64, device=dev)
 
-    def measure(n):
+    def measure(n, dump=False):
         """One workload (n^3 grid, this rank's P points) by the bench contract: grid generated on
         rank 0 and replicated by ONE broadcast, W warm-up steps, EXACTLY K timed steps between
-        barrier + synchronize pairs, max over ranks.  Returns (record pieces, handle, spec)."""
+        barrier + synchronize pairs, max over ranks.  `dump`: what the last timed step computed is
+        written to --dump-outputs.  Returns (record pieces, handle, spec)."""
         spec = build_spec("linear", "regular", n, NDIMS, False, seed=1)
         vals_dev = torch.empty(n**NDIMS, dtype=torch.float64, device=dev)
         if rank == 0:
@@ -954,11 +992,17 @@ def worker(args):
         elapsed = time.perf_counter() - t0
         step_ms = [a.elapsed_time(b) for a, b in ev]
         kernel_ms_local = float(np.mean(step_ms))
+        if dump and args.dump_outputs:
+            # before anything else launches on `out`
+            idx = torch.from_numpy(dump_index(P, rank, world)).to(dev)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, dump_name(rank)), out[idx].cpu().numpy())
+            del idx
         # Same workload on ONE GPU with the others idle (rank 0 alone), so that the N-rank figure can
         # be read against an identical single-GPU one taken in the same run.  AFTER the timed region:
         # the ranks that idle at this barrier come back with cold clocks.
         solo_ms = None
-        if world > 1:
+        if world > 1 and args.full:
             if rank == 0:
                 solo_ms = float(np.mean(time_launches(torch, it, obs, out, launches=max(20, min(args.steps, 200)),
                                                       finish_each=True)))
@@ -981,10 +1025,10 @@ def worker(args):
     # protocol as a second block ("cfg5") whenever N > 1; at N = 1 its shard is a row of configs[].
     workload = args.workload if args.workload != "auto" else "cfg2"
     n = args.grid or WORKLOADS[workload][0]
-    m, it, spec = measure(n)
+    m, it, spec = measure(n, dump=True)
     elapsed, kernel_ms, per_rank_ms, solo_ms = m["elapsed"], m["kernel_ms"], m["per_rank_ms"], m["solo_ms"]
     second = None
-    if world > 1 and workload == "cfg2" and not args.grid and not args.no_cfg5:
+    if args.full and world > 1 and workload == "cfg2" and not args.grid and not args.no_cfg5:
         m5, it5, _ = measure(WORKLOADS["cfg5"][0])
         if rank == 0:
             tb5, si5, sj5 = it5.table_layout()
@@ -1010,20 +1054,6 @@ def worker(args):
         total_points = P * world * args.steps
         value = total_points / elapsed / 1e6
         achieved = P * bpp / (kernel_ms * 1e-3) / 1e9
-
-        # Measured device-copy bandwidth (1 read + 1 write of 0.8 GB), reported beside the nominal peak.
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        scratch = torch.empty_like(out)
-        scratch.copy_(obs[0])
-        best = float("inf")
-        for _ in range(5):
-            c0.record()
-            scratch.copy_(obs[0])
-            c1.record()
-            torch.cuda.synchronize()
-            best = min(best, c0.elapsed_time(c1))
-        copy_gbps = 2 * 8 * P / (best * 1e-3) / 1e9
-        del scratch
 
         traffic, traffic_src = committed_traffic(kernel, P, n, tbytes)
         rec = {
@@ -1082,10 +1112,24 @@ def worker(args):
                 "kernel_ms_max": round(float(np.max(m["step_ms"])), 4),
                 "kernel_ms_first_steps": [round(x, 3) for x in m["step_ms"][:32]],
                 "algorithmic_bytes_per_point": bpp,
-                "measured_copy_GBps": round(copy_gbps, 1),
-                "frac_of_measured_copy": round(achieved / copy_gbps, 4),
             },
         }
+        if args.full:
+            # Measured device-copy bandwidth (1 read + 1 write of 0.8 GB), reported beside the nominal peak.
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            scratch = torch.empty_like(out)
+            scratch.copy_(obs[0])
+            best = float("inf")
+            for _ in range(5):
+                c0.record()
+                scratch.copy_(obs[0])
+                c1.record()
+                torch.cuda.synchronize()
+                best = min(best, c0.elapsed_time(c1))
+            copy_gbps = 2 * 8 * P / (best * 1e-3) / 1e9
+            del scratch
+            rec["roofline"]["measured_copy_GBps"] = round(copy_gbps, 1)
+            rec["roofline"]["frac_of_measured_copy"] = round(achieved / copy_gbps, 4)
         if second is not None:
             rec["cfg5"] = second
         if world > 1 and solo_ms:
@@ -1093,7 +1137,7 @@ def worker(args):
                 "kernel_ms": round(solo_ms, 4), "Mpoints_per_s": round(P / solo_ms / 1e3, 1),
                 "note": "rank 0 alone on its GPU, the other ranks idle at a barrier, same grid and batch: "
                         "value / (n_gpus x this) is the scaling efficiency on an identical workload"}
-        if world == 1:
+        if world == 1 and args.full:
             # >= 0.5 s of back-to-back launches (the K-step region above may be only 20 launches)
             ms = time_launches(torch, it, obs, out, seconds=args.sustain_seconds)
             sk = float(np.mean(ms))

@@ -1,9 +1,10 @@
 """Host-side pieces of bench.py that need no GPU: the compact per-configuration summary the record carries inside
-`roofline` (so that a parser which keeps only the contract's keys still sees every configuration), and the device check
-of the multi-GPU record."""
+`roofline` (so that a parser which keeps only the contract's keys still sees every configuration), the device check
+of the multi-GPU record, the options of a plain run, and the sample of results that --dump-outputs writes."""
 import os
 import sys
 
+import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -38,3 +39,26 @@ def test_distinct_device_check():
     bench.check_distinct_devices(nopci, 8)
     with pytest.raises(SystemExit):
         bench.check_distinct_devices([dict(d, pci=None, cuda_device=0) for d in devs], 8)
+
+
+def test_plain_run_is_the_default_and_steps_are_checked():
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "some/dir"])
+    assert a.full is True and a.dump_outputs == "some/dir"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    small = bench.dump_index(1000, 0, 1)
+    assert small.tolist() == list(range(1000))
+    for world in (1, 2, 3, 8):
+        P = 100_000_000
+        idx = [bench.dump_index(P, r, world) for r in range(world)]
+        assert sum(i.size for i in idx) * 8 <= 64 * 2**20  # f64 results over all ranks
+        for r, i in enumerate(idx):
+            assert i.min() >= 0 and i.max() < P and np.all(np.diff(i) >= 0)
+            assert np.array_equal(i, bench.dump_index(P, r, world))  # the same points on every run
+    assert not np.array_equal(bench.dump_index(10**8, 0, 2), bench.dump_index(10**8, 1, 2))
+    assert bench.dump_name(0) == "out.npy" and bench.dump_name(3) == "out_rank3.npy"

@@ -156,8 +156,8 @@ def test_bench_single_process_claims_no_broadcast():
 
 @pytest.mark.gpu
 def test_bench_one_rank_per_gpu_smoke():
-    """`bench.py --gpus N --steps 2` with N = min(device_count, 8) > 1: the driver's multi-GPU command in
-    its spawned form (N fresh ranks over RCCL, grid broadcast, cfg5 block).  Skipped on a single-GPU box,
+    """`bench.py --gpus N --steps 2 --full` with N = min(device_count, 8) > 1: the driver's multi-GPU command in
+    its spawned form (N fresh ranks over RCCL, grid broadcast, with --full the cfg5 block).  Skipped on a single-GPU box,
     where `test_bench_force_dist_over_rccl_records_what_happened` runs the same calls with one rank."""
     n = rccl_world_size(_visible_gpus())
     if n < 2:
@@ -165,7 +165,7 @@ def test_bench_one_rank_per_gpu_smoke():
     env = _env()
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-configs", "--no-ablate", "--sustain-seconds", "0.05"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])

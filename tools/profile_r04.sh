@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/prof_r04
 rm -rf "$OUT" && mkdir -p "$OUT"
 PY=python3
 echo "A" ; date
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $PY $R/bench.py --steps 20 --warmup 5 > $OUT/stats_bench.json 2> $OUT/stats.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $PY $R/bench.py --steps 20 --warmup 5 --full > $OUT/stats_bench.json 2> $OUT/stats.err
 echo "B" ; date
 for c in FETCH_SIZE WRITE_SIZE; do
   if [ -x $R/tools/tune_linear3d ]; then
