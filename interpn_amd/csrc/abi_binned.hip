@@ -102,12 +102,12 @@ interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, h
       bool ok = !recorded || hipEventSynchronize(ev) == hipSuccess;
       if (ok) {
         pool_free(h->device, old);
-        h->last_probe_word = nullptr;
         freed = true;
         ok = pool_alloc(h->device, &fresh, need) == hipSuccess;
       }
       if (!ok) (void)hipGetLastError();
       lk.lock();
+      if (freed) h->sampling.last_word = nullptr;
       pick->busy = false;
       if (!ok) {
         if (freed) { pick->scratch = nullptr; pick->bytes = 0; pick->recorded = false; }  // else the old block stays as it was
@@ -119,7 +119,7 @@ interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, h
       pick->scratch = fresh;
       pick->bytes = need;
       pick->totals_clean = false;
-        pick->sweep_clean = false;
+      pick->sweep_clean = false;
       pick->recorded = false;
       h->scratch_allocs.fetch_add(1);
     }
@@ -131,6 +131,23 @@ interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, h
   pick->busy = true;
   pick->stamp = ++h->bin_uses;
   return pick;
+}
+
+// Ends an evaluation's use of a block from take_bin_slot: whatever was enqueued — also a sequence cut short by a failure — is
+// followed by the block's event, so that the next user of the block on another stream waits for it.  `staged`: the block's
+// stage events were recorded by this use (option stage_timing).
+void release_bin_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot, hipStream_t stream, bool staged) {
+  std::lock_guard<std::mutex> lk(h->bin_mu);
+  if (hipEventRecord(slot->event, stream) == hipSuccess) {
+    slot->recorded = true;
+  } else {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(stream);  // no event behind the work: make it complete before anyone reuses the block
+    slot->recorded = false;
+  }
+  slot->last_stream = stream;
+  slot->busy = false;
+  slot->staged = staged;
 }
 
 // Binned evaluation of the tiled multicubic kernels on device-resident points (interpn_host.h).
@@ -217,7 +234,6 @@ int eval_device_binned(interpn_hip_interp* h, const void* const* obs, void* out,
   hipError_t err = hipSuccess;
   // per-stage timing on request (single-slice evaluations only)
   hipEvent_t* stage = nullptr;
-  slot->staged = false;
   if (g.cfg.stage_timing && npoints <= slice) {
     bool okev = true;
     for (hipEvent_t& e : slot->stage)
@@ -231,73 +247,54 @@ int eval_device_binned(interpn_hip_interp* h, const void* const* obs, void* out,
     for (int d = 0; d < g.ndims; ++d) src[d] = static_cast<const char*>(obs[d]) + begin * elem;
     const unsigned* index = nullptr;
     char* dst = static_cast<char*>(out) + begin * elem;
-    if (column3_go) {  // 3-D: the cell's column of n2 tiles (cubic3_column.h)
-      const size_t q3 = cubic3_column_part_points();
-      const size_t max_parts3 = 4 * (count / q3) + (size_t)plan.nbins + 1;
-      BinExtras extras3;
-      err = bin_points(g, plan, src, count, slot->scratch, sorted, &index, stream, &extras3, (unsigned)q3, stage, slot->totals_clean);
-      slot->totals_clean = err == hipSuccess;
-      slot->sweep_clean = false;
-      if (err != hipSuccess) break;
-      if (g.dtype == kF64)
-        err = launch_cubic3_column<double>(*use, plan, extras3, index, reinterpret_cast<double*>(dst), count, max_parts3, h->first_bad, begin, stream);
-      else
-        err = launch_cubic3_column<float>(*use, plan, extras3, index, reinterpret_cast<float*>(dst), count, max_parts3, h->first_bad, begin, stream);
-      continue;
-    }
-    if (column) {
+    // the column kernels (3-D: the cell's column of n2 tiles, cubic3_column.h; 4-D: cubic_column.h) take their points in
+    // parts of at most q points per bin
+    BinExtras extras;
+    size_t q = 0;
+    if (column3_go) {
+      q = cubic3_column_part_points();
+    } else if (column) {
       // a bin is cut into equal parts of at most 16 points per thread of the column workgroup (the
       // registers of its local sort); two such workgroups share a CU, the dispatcher hands parts
       // to whichever frees up
       ColumnPlan cplan;
       if (!cubic_column_plan(*use, &cplan)) { err = hipErrorInvalidValue; break; }
-      size_t q = cplan.part_points;
+      q = cplan.part_points;
       if (g.cfg.column_part > 0 && (size_t)g.cfg.column_part < q) q = (size_t)g.cfg.column_part;
-      const size_t max_parts = 4 * (count / q) + (size_t)plan.nbins + 1;  // upper bound (the scan cuts the last bins finer)
-      BinExtras extras;
       if (column_keys_in_index(*use) && count <= kColumnKeySlicePoints && cplan.q3 * (g.n[2] - 1) <= 256) {
         extras.key_q3 = cplan.q3;
         extras.key_sh3 = cplan.sh3;
       }
-      err = bin_points(g, plan, src, count, slot->scratch, sorted, &index, stream, &extras, (unsigned)q, stage, slot->totals_clean);
-      slot->totals_clean = err == hipSuccess;
-      slot->sweep_clean = false;
-      if (err != hipSuccess) break;
+    }
+    err = bin_points(g, plan, src, count, slot->scratch, sorted, &index, stream, column3_go || column ? &extras : nullptr, (unsigned)q, stage,
+                     slot->totals_clean);
+    slot->totals_clean = err == hipSuccess;
+    slot->sweep_clean = false;
+    if (err != hipSuccess) break;
+    const size_t max_parts = q ? 4 * (count / q) + (size_t)plan.nbins + 1 : 0;  // (column kernels) upper bound: the scan cuts the last bins finer
+    if (column3_go) {
+      if (g.dtype == kF64)
+        err = launch_cubic3_column<double>(*use, plan, extras, index, reinterpret_cast<double*>(dst), count, max_parts, h->first_bad, begin, stream);
+      else
+        err = launch_cubic3_column<float>(*use, plan, extras, index, reinterpret_cast<float*>(dst), count, max_parts, h->first_bad, begin, stream);
+    } else if (column) {
       if (g.dtype == kF64)
         err = launch_cubic_column<double>(*use, plan, extras, index, reinterpret_cast<double*>(dst), count, max_parts, h->first_bad, begin, stream);
       else
         err = launch_cubic_column<float>(*use, plan, extras, index, reinterpret_cast<float*>(dst), count, max_parts, h->first_bad, begin, stream);
-      continue;
-    }
-    err = bin_points(g, plan, src, count, slot->scratch, sorted, &index, stream, nullptr, 0, stage, slot->totals_clean);
-    slot->totals_clean = err == hipSuccess;
-      slot->sweep_clean = false;
-    if (err != hipSuccess) break;
-    if (g.dtype == kF64)
+    } else if (g.dtype == kF64) {
       err = launch_cubic_brick<double>(*use, reinterpret_cast<const double* const*>(sorted), reinterpret_cast<double*>(dst), count,
                                        h->first_bad, stream, index, begin);
-    else
+    } else {
       err = launch_cubic_brick<float>(*use, reinterpret_cast<const float* const*>(sorted), reinterpret_cast<float*>(dst), count,
                                       h->first_bad, stream, index, begin);
+    }
   }
-  if (stage && err == hipSuccess && hipEventRecord(stage[4], stream) == hipSuccess) slot->staged = true;
-  // Whatever was enqueued — also a sequence cut short by a failure — is followed by the block's
-  // event, so that the next user of the block on another stream waits for it.
-  {
+  release_bin_slot(h, slot, stream, stage && err == hipSuccess && hipEventRecord(stage[4], stream) == hipSuccess);
+  if (err == hipSuccess) {
     std::lock_guard<std::mutex> lk(h->bin_mu);
-    if (hipEventRecord(slot->event, stream) == hipSuccess) {
-      slot->recorded = true;
-    } else {
-      (void)hipGetLastError();
-      (void)hipStreamSynchronize(stream);  // no event behind the work: make it complete before anyone reuses the block
-      slot->recorded = false;
-    }
-    slot->last_stream = stream;
-    slot->busy = false;
-    if (err == hipSuccess) {
-      h->desc.tag = use->tag;
-      h->desc.last_binned = 1;
-    }
+    h->desc.tag = use->tag;
+    h->desc.last_binned = 1;
   }
   if (err != hipSuccess) {
     (void)hipGetLastError();
@@ -412,7 +409,7 @@ int interpn_hip_reserve(interpn_hip_interp* h, size_t npoints, int nstreams) {
     if (sl.bytes >= need || sl.busy) continue;
     if (sl.recorded) HIP_TRY(hipEventSynchronize(sl.event));
     pool_free(h->device, sl.scratch);
-    h->last_probe_word = nullptr;
+    h->sampling.last_word = nullptr;
     sl.scratch = nullptr;
     sl.bytes = 0;
     sl.totals_clean = false;

@@ -162,16 +162,20 @@ struct interpn_hip_interp {
   unsigned long long bin_uses = 0;
   interpn_hip_interp() { bin_slots.reserve(kMaxBinSlots); }
   std::atomic<long long> evals_binned{0}, evals_in_place{0}, evals_sweep{0}, scratch_allocs{0};
-  // thinning the sample out (option sweep_probe = 2; guarded by bin_mu): the sampling kernel also stores (seq << 1 | coherent)
-  // into this pinned word; the host looks at it before the next launch — no synchronisation, a verdict that has not landed
-  // yet simply is not known yet
-  unsigned long long* probe_host = nullptr;
-  unsigned* probe_host_dev = nullptr;
-  unsigned probe_seq = 0, probe_seen = 0;
-  int probe_streak = 0;     // samples in a row that came out unordered
-  int probe_streak_coherent = 0;  // ... that came out coherent
-  int probe_skipped = 0;    // automatic launches since the last sample
-  const void* last_probe_word = nullptr;  // device word holding the verdict of the most recent gated launch's sampling kernel (option "sweep_probe_took_brick"; tests, bench)
+  // The device-side sample in front of automatic sweep launches (abi_sweep.hip; guarded by bin_mu).  Thinning it out
+  // (option sweep_probe = 2): the sampling kernel also stores (seq << 1 | coherent) into the pinned word `host`; the host
+  // looks at it before the next launch — no synchronisation, a verdict that has not landed yet simply is not known yet.
+  struct SweepSampling {
+    unsigned long long* host = nullptr;
+    unsigned* host_dev = nullptr;  // its device address (null: no host view of the verdicts, every launch is sampled)
+    unsigned seq = 0, seen = 0;
+    int streak = 0;           // samples in a row that came out unordered
+    int streak_coherent = 0;  // ... that came out coherent
+    int skipped = 0;          // automatic launches since the last sample
+    // the verdict word of the most recent automatic launch's sample, inside a scratch block (option "sweep_probe_took_brick";
+    // tests, bench); null when that launch was not sampled or its block has been freed since
+    const void* last_word = nullptr;
+  } sampling;
 };
 
 namespace interpn_abi {
@@ -278,6 +282,7 @@ hipError_t wait_status_word(hipStream_t s, const unsigned long long* word);
 // abi_binned.hip
 int binned_applies(const GridDesc& g, size_t npoints);
 interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, hipStream_t stream, bool may_alloc, int* why);
+void release_bin_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot, hipStream_t stream, bool staged);
 
 // abi_sweep.hip
 int eval_device_sweep(interpn_hip_interp* h, const void* const* obs, void* out, size_t npoints, hipStream_t stream,

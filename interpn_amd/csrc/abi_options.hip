@@ -161,12 +161,21 @@ int interpn_hip_get_option(const interpn_hip_interp* h, const char* name, long l
   if (!strcmp(name, "evals_sweep")) { *value = h->evals_sweep.load(); return INTERPN_HIP_OK; }
   if (!strcmp(name, "sweep_table_bytes")) { *value = h->desc.sweep_bricks ? (long long)h->desc.sweep_table_bytes : 0; return INTERPN_HIP_OK; }
   if (!strcmp(name, "sweep_probe_took_brick")) {  // read-only, synchronises the device: 1 / 0 = what the last gated launch's sample decided, -1 = the last sweep launch was not gated
+    // (under bin_mu, and only from a block that nobody is enqueueing into: a block is freed or re-used only when taken)
+    interpn_hip_interp* hm = const_cast<interpn_hip_interp*>(h);
+    std::lock_guard<std::mutex> lk(hm->bin_mu);
+    const unsigned char* word = static_cast<const unsigned char*>(hm->sampling.last_word);
+    bool idle = false;
+    for (const auto& sl : hm->bin_slots) {
+      const unsigned char* base = static_cast<const unsigned char*>(sl.scratch);
+      if (!sl.busy && word && base && word >= base && word + sizeof(unsigned) <= base + sl.bytes) idle = true;
+    }
     *value = -1;
-    if (h->last_probe_word) {
+    if (idle) {
       DeviceGuard guard(h->device);
       if (!guard.ok()) return INTERPN_HIP_ERR_NO_DEVICE;
       unsigned w = 0;
-      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&w, h->last_probe_word, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return INTERPN_HIP_ERR_INVALID_ARGUMENT; }
+      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&w, word, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return INTERPN_HIP_ERR_INVALID_ARGUMENT; }
       *value = w ? 1 : 0;
     }
     return INTERPN_HIP_OK;
@@ -174,7 +183,7 @@ int interpn_hip_get_option(const interpn_hip_interp* h, const char* name, long l
   if (!strcmp(name, "sweep_probe_streak")) {  // read-only: samples in a row whose verdict was "unordered", as far as the host knows (thinned policy)
     interpn_hip_interp* hm = const_cast<interpn_hip_interp*>(h);
     std::lock_guard<std::mutex> lk(hm->bin_mu);
-    *value = hm->probe_streak;
+    *value = hm->sampling.streak;
     return INTERPN_HIP_OK;
   }
   if (!strcmp(name, "sweep_cell")) { *value = h->desc.sweep_bricks ? h->desc.sweep_cell : 0; return INTERPN_HIP_OK; }  // 0: 2 x 2 x KW bricks, 2: 2 x 4 x 4 (f32)

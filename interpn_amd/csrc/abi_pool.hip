@@ -1,5 +1,7 @@
 // Per-device pool of device blocks, streams, pinned words and small-batch staging buffers; device
 // properties; the thread's last HIP error.  (C ABI internals, see abi_internal.h.)
+#include <map>
+
 #include "abi_internal.h"
 
 using namespace interpn;
@@ -335,3 +337,21 @@ int resolve_device(int device, int* out) {
 }
 
 }  // namespace interpn_abi
+
+namespace interpn {
+
+hipError_t allow_dynamic_lds(const void* kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return hipSuccess;  // (the default)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError();
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, size_t> granted;  // (kernel, device) -> the largest size opted in to
+  std::lock_guard<std::mutex> lk(mu);
+  size_t& have = granted[{kernel, dev}];
+  if (have >= bytes) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) have = bytes;
+  return e;
+}
+
+}  // namespace interpn

@@ -217,21 +217,26 @@ inline Thresholds thresholds(const LaunchConfig& c) {
   return t;
 }
 
-// Sweep evaluation (k_linear_sweep.hip)
-bool sweep_layout(const GridDesc& g, int* si, int* sj, int* cell);
+// Sweep evaluation of large device-resident batches: four kernel families, picked by launch_sweep / sweep_applies
+// (abi_sweep.hip), each 0 = never for this handle, 1 = not for this batch, 2 = yes.  `work`: a zeroed SweepWork block
+// (sweep_work_bytes) that no other launch in flight uses; obs / out 16-byte aligned (eval_device_sweep checks).
 int sweep_applies(const GridDesc& g, size_t npts);
+hipError_t launch_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
+                        void* work, hipStream_t stream);
 size_t sweep_work_bytes();
-int nearest_sweep_applies(const GridDesc& g, size_t npts);  // k_nearest.hip (2-D / 3-D nearest neighbour, regular grids)
-hipError_t launch_nearest_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
+bool sweep_layout(const GridDesc& g, int* si, int* sj, int* cell);
+int linear3_sweep_applies(const GridDesc& g, size_t npts);  // k_linear_sweep.hip (3-D multilinear)
+hipError_t launch_linear3_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
                                 void* work, hipStream_t stream);
 int linear2_sweep_applies(const GridDesc& g, size_t npts);  // k_linear2_brick.hip (2-D multilinear, regular grids)
 hipError_t launch_linear2_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
                                 void* work, hipStream_t stream);
-int cubic_sweep_applies(const GridDesc& g, size_t npts);   // k_cubic_sweep.hip (3-D multicubic; sweep_applies / launch_linear_sweep hand cubic handles over)
+int nearest_sweep_applies(const GridDesc& g, size_t npts);  // k_nearest.hip (2-D / 3-D nearest neighbour, regular grids)
+hipError_t launch_nearest_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
+                                void* work, hipStream_t stream);
+int cubic_sweep_applies(const GridDesc& g, size_t npts);    // k_cubic_sweep.hip (2-D / 3-D multicubic)
 hipError_t launch_cubic_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
                               void* work, hipStream_t stream);
-hipError_t launch_linear_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
-                               void* work, hipStream_t stream);
 // Automatic sweep launches of the handles sweep_probe_applies() names: the sampling kernel whose verdict (a word of the
 // scratch block, at this offset) gates the sweep launch (GridDesc::sweep_gated) and the one-pass launch
 // (GridDesc::launch_gate) enqueued behind it
@@ -239,6 +244,10 @@ bool sweep_probe_applies(const GridDesc& g);
 hipError_t launch_sweep_probe(const GridDesc& g, const void* const* obs, size_t npts, void* work, hipStream_t stream,
                               unsigned* host_word = nullptr, unsigned seq = 0);
 size_t sweep_probe_word_offset();
+
+// Lets `kernel` launch with `bytes` of dynamic LDS on the current device (more than the default 64 KiB needs the opt-in,
+// hipFuncSetAttribute: microseconds, so it is made once per kernel, device and larger size; abi_pool.hip).
+hipError_t allow_dynamic_lds(const void* kernel, size_t bytes);
 
 template <typename T>
 hipError_t launch_linear_regular(const GridDesc& g, const T* const* obs, T* out, size_t npts,

@@ -9,7 +9,6 @@
 // written by consecutive lanes instead of single scattered elements.  The order of points inside a bin is not
 // deterministic; results do not depend on it (a point's result depends on its coordinates only,
 // src/multicubic/regular.rs:297-313).
-#include <atomic>
 
 #include "interpn_kernels.h"
 
@@ -551,19 +550,9 @@ hipError_t bin_points_n(const BinParams& p, const void* const* obs, size_t npts,
       // needed, not to the maximum.  A device (or an opt-in) that does not give it takes the direct form.
       bool use_staged = p.nbins <= kScatThreads && staged && staged_lds <= kStagedLdsMax && staged_lds + 1024 <= lds_per_cu;
       auto kern = k_bin_scatter_records_staged<T, N, (int)kRecChunk>;
-      if (use_staged && staged_lds > 64 * 1024) {
-        static std::atomic<unsigned long long> opted_bytes[64];  // per device: the largest size opted in to so far
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
-        if (dev < 0 || dev >= 64 || opted_bytes[dev].load() < staged_lds) {
-          if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)staged_lds) != hipSuccess) {
-            (void)hipGetLastError();
-            use_staged = false;
-          } else if (dev >= 0 && dev < 64) {
-            unsigned long long cur = opted_bytes[dev].load();
-            while (cur < staged_lds && !opted_bytes[dev].compare_exchange_weak(cur, staged_lds)) {}
-          }
-        }
+      if (use_staged && allow_dynamic_lds(reinterpret_cast<const void*>(kern), staged_lds) != hipSuccess) {
+        (void)hipGetLastError();
+        use_staged = false;
       }
       if (use_staged) {
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(kScatThreads), staged_lds, stream, a);

@@ -1,6 +1,4 @@
 // Launcher of the LDS-column multicubic kernel for sorted 4-D points (cubic_column.h).
-#include <mutex>
-
 #include "cubic_column.h"
 
 namespace interpn {
@@ -9,32 +7,6 @@ namespace {
 // LDS of a CU, and what a workgroup of this kernel declares statically per wave group (histogram +
 // control words, rounded up)
 constexpr size_t kColumnStaticPerGroup = 4096 + 256;
-
-// More than 64 KiB of dynamic LDS needs the opt-in, once per kernel and device: remembered here so
-// that the launch path does not pay the call (microseconds) every time.
-hipError_t column_lds_opt_in(const void* kernel, int groups, size_t cu_lds) {
-  struct Seen { const void* fn; unsigned long long devices; };
-  static std::mutex mu;
-  static Seen seen[32] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = -1;
-  Seen* slot = nullptr;
-  if (dev >= 0) {
-    std::lock_guard<std::mutex> lk(mu);
-    for (Seen& s : seen) {
-      if (s.fn == kernel) { slot = &s; break; }
-      if (!s.fn) { s.fn = kernel; slot = &s; break; }
-    }
-    if (slot && ((slot->devices >> dev) & 1ull)) return hipSuccess;
-  }
-  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)(cu_lds - (size_t)groups * kColumnStaticPerGroup));
-  if (e == hipSuccess && slot) {
-    std::lock_guard<std::mutex> lk(mu);
-    slot->devices |= 1ull << dev;
-  }
-  return e;
-}
 }  // namespace
 
 // How the column evaluation runs on this grid (cubic_column.h): one persistent workgroup per CU
@@ -218,7 +190,8 @@ hipError_t launch_cubic_column(const GridDesc& g, const BinPlan& plan, const Bin
   if (wgs < 1) wgs = 1;
   auto prepare = [&](auto kernel) -> hipError_t {
     if (lds <= 64 * 1024) return hipSuccess;
-    return column_lds_opt_in(reinterpret_cast<const void*>(kernel), cp.groups, thresholds(g.cfg).column_lds);
+    // the CU's LDS less what the workgroup declares statically: the most any plan of this kernel asks for
+    return allow_dynamic_lds(reinterpret_cast<const void*>(kernel), thresholds(g.cfg).column_lds - (size_t)cp.groups * kColumnStaticPerGroup);
   };
   hipError_t e = hipSuccess;
 #define GO_R(RECT, FMA, TH, GR)                                                                                  \

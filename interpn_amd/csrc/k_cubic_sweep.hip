@@ -1,6 +1,4 @@
 // Host side of the sweep evaluation of 2-D and 3-D multicubic batches (cubic_sweep.h): when it applies and the launcher.
-#include <atomic>
-
 #include "cubic_sweep.h"
 
 namespace interpn {
@@ -67,31 +65,17 @@ int cubic_sweep_applies(const GridDesc& g, size_t npts) {
 }
 
 template <typename T, int N, bool RECT, bool FMA, int K = cubic_sweep_rows<T, RECT, N>(), int KL = cubic_sweep_parked<T, RECT, N>(), int TH = cubic_sweep_threads<T, RECT, N>()>
-static hipError_t go(const GridDesc& g, CubicSweepArgs<T, N> s, unsigned cus, hipStream_t stream) {
-  {
-    const size_t chunk = (size_t)64 * (K + KL);
-    const size_t rounds = (s.r.npts + chunk - 1) / chunk;
-    if (rounds > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-    s.r.rounds = (unsigned)rounds;
-    s.r.per_shard = (s.r.rounds + 7u) / 8u;
-  }
-  unsigned blocks = cus;
-  {
-    const unsigned need = (s.r.rounds + (TH / 64) - 1) / (TH / 64);
-    if (blocks > need) blocks = need;
-  }
+static hipError_t go(const GridDesc& g, CubicSweepArgs<T, N> s, void* work, hipStream_t stream) {
+  // 40 us: a round of ten cubic rows
+  if (!sweep_schedule(s.r, g, s.r.npts, (size_t)64 * (K + KL), 4000, work)) return hipErrorInvalidValue;
+  const unsigned blocks = sweep_blocks(g, s.r.rounds, TH);
   auto kern = k_cubic_sweep<T, RECT, FMA, K, KL, TH, N>;
   const size_t lds = (size_t)CubicSweepLds<T, K, KL, N>::kWave * (TH / 64) + CubicSweepLds<T, K, KL, N>::kWorkgroup + ((RECT && s.c.ax.use_lds) ? (size_t)s.c.ax.image_bytes : 0);
-  static std::atomic<unsigned long long> opted{0};  // bit per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError();
-  if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || !((opted.load() >> dev) & 1ull))) {
-    size_t most = (size_t)CubicSweepLds<T, K, KL, N>::kWave * (TH / 64) + CubicSweepLds<T, K, KL, N>::kWorkgroup + (RECT ? kCubicSweepAxisLds : 0);
-    if (g.cfg.lds_per_cu > 0 && most > (size_t)g.cfg.lds_per_cu) most = (size_t)g.cfg.lds_per_cu;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev);
-  }
+  // opted in to the largest this instantiation ever asks for (its waves' regions + the axis image budget, at most the CU's LDS)
+  size_t most = (size_t)CubicSweepLds<T, K, KL, N>::kWave * (TH / 64) + CubicSweepLds<T, K, KL, N>::kWorkgroup + (RECT ? kCubicSweepAxisLds : 0);
+  if (g.cfg.lds_per_cu > 0 && most > (size_t)g.cfg.lds_per_cu) most = (size_t)g.cfg.lds_per_cu;
+  hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), most);
+  if (e != hipSuccess) return e;
   if (N == 3) g.tag.set("k_cubic_sweep", {RECT, FMA, K, KL, TH}, 0b00011u);
   else g.tag.set("k_cubic_sweep", {RECT, FMA, K, KL, TH, N}, 0b000011u);
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(TH), lds, stream, s);
@@ -136,13 +120,7 @@ static hipError_t launch_t(const GridDesc& g, const void* const* obs, void* out,
   }
   a.nbj = nb[1];
   if constexpr (N == 3) a.plane_stride[2] = nb[0] * nb[1] * 16u;  // table[plane (dim 2)][bi][bj][16]
-  s.fastdiv = g.kind == kRectilinear ? 0u : 1u;
-  for (int d = 0; d < N; ++d) {
-    const volatile T one = (T)1;  // one IEEE division in T, at run time
-    s.rstep[d] = g.kind == kRectilinear ? (T)0 : one / (T)g.step[d];
-    const double mag = g.step[d] < 0 ? -g.step[d] : g.step[d];
-    if (!(mag >= StepCellRange<T>::lo && mag <= StepCellRange<T>::hi)) s.fastdiv = 0;
-  }
+  step_reciprocals(g, s.rstep, &s.fastdiv);
   a.ax.use_lds = 0;
   a.ax.image = nullptr;
   a.ax.image_bytes = 0;
@@ -152,33 +130,17 @@ static hipError_t launch_t(const GridDesc& g, const void* const* obs, void* out,
   if (g.kind == kRectilinear) {
     (void)fill_axis_args<T, N>(g, a.ax);
     if (a.ax.use_lds && (a.ax.image_bytes > kCubicSweepAxisLds || (long long)(cubic_sweep_wave_lds(g) + a.ax.image_bytes) > g.cfg.lds_per_cu)) a.ax.use_lds = 0;
-    const double span = g.bound_hi[KD] - g.bound_lo[KD];
-    r.key_start = (T)g.bound_lo[KD];
-    r.key_scale = span > 0 ? (T)((double)(g.n[KD] - 1) / span) : (T)0;
-  } else {
-    r.key_start = (T)g.start[KD];
-    r.key_scale = (T)(1.0 / g.step[KD]);
   }
-  if (!(r.key_scale > 0) || !(r.key_scale < (T)1e30)) r.key_scale = 0;  // every point in bin 0: still correct
+  sweep_key(g, KD, &r.key_start, &r.key_scale);
   r.key_cells = g.n[KD] - 2;
-  r.key_shift = 0;
-  while (((g.n[KD] - 2) >> r.key_shift) >= 64) ++r.key_shift;
-  r.period = g.cfg.sweep_period > 0 ? (unsigned)g.cfg.sweep_period : 0u;
-  r.period_default = 4000;  // 40 us: a round of ten cubic rows (the kernel measures from its first launch on)
-  r.gated = g.sweep_gated ? 1u : 0u;
-  r.stamps = nullptr;
-  r.work = static_cast<SweepWork*>(work);
-  const unsigned cus = (unsigned)(g.cfg.num_cus > 0 ? g.cfg.num_cus : 256);
-  if (g.kind == kRegular) return g.fma ? go<T, N, false, true>(g, s, cus, stream) : go<T, N, false, false>(g, s, cus, stream);
-  return g.fma ? go<T, N, true, true>(g, s, cus, stream) : go<T, N, true, false>(g, s, cus, stream);
+  r.key_shift = sweep_key_shift(r.key_cells);
+  if (g.kind == kRegular) return g.fma ? go<T, N, false, true>(g, s, work, stream) : go<T, N, false, false>(g, s, work, stream);
+  return g.fma ? go<T, N, true, true>(g, s, work, stream) : go<T, N, true, false>(g, s, work, stream);
 }
 
 hipError_t launch_cubic_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
                               void* work, hipStream_t stream) {
-  if (g.method != kCubic || (g.ndims != 3 && g.ndims != 2) || !work || npts == 0) return hipErrorInvalidValue;
-  for (int d = 0; d < g.ndims; ++d)
-    if (reinterpret_cast<uintptr_t>(obs[d]) % 16) return hipErrorInvalidValue;  // the caller checked (abi_sweep.hip)
-  if (reinterpret_cast<uintptr_t>(out) % 16) return hipErrorInvalidValue;
+  if (g.ndims != 3 && g.ndims != 2) return hipErrorInvalidValue;
   if (g.ndims == 2) return g.dtype == kF64 ? launch_t<double, 2>(g, obs, out, npts, first_bad, work, stream) : launch_t<float, 2>(g, obs, out, npts, first_bad, work, stream);
   return g.dtype == kF64 ? launch_t<double, 3>(g, obs, out, npts, first_bad, work, stream) : launch_t<float, 3>(g, obs, out, npts, first_bad, work, stream);
 }

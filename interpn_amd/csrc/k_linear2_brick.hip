@@ -9,7 +9,6 @@
 // swap the piece they hold for the other point with a quad-permute DPP move — no LDS.  Arithmetic
 // and operation order are the reference's (src/multilinear/regular.rs:296-404), results are
 // bit-identical to the C-order kernel.
-#include <atomic>
 #include <type_traits>
 
 #include "lane_axes.h"
@@ -356,45 +355,24 @@ static hipError_t launch2_t(const GridDesc& g, const void* const* obs, void* out
   r.out = static_cast<T*>(out);
   s.first_bad = first_bad;
   r.npts = npts;
-  s.fastdiv = 1;
   for (int d = 0; d < 2; ++d) {
     r.obs[d] = static_cast<const T*>(obs[d]);
     s.start[d] = (T)g.start[d];
     r.absent[d] = s.start[d];
     s.step[d] = (T)g.step[d];
     s.n[d] = g.n[d];
-    const volatile T one = (T)1;
-    s.rstep[d] = one / (T)g.step[d];
-    const double mag = g.step[d] < 0 ? -g.step[d] : g.step[d];
-    if (!(mag >= StepCellRange<T>::lo && mag <= StepCellRange<T>::hi)) s.fastdiv = 0;
   }
+  step_reciprocals(g, s.rstep, &s.fastdiv);
   s.nbj = g.brick_nb[1];
-  r.key_start = (T)g.start[0];
-  r.key_scale = (T)(1.0 / g.step[0]);
-  if (!(r.key_scale > 0) || !(r.key_scale < (T)1e30)) r.key_scale = 0;
+  sweep_key(g, 0, &r.key_start, &r.key_scale);
   r.key_cells = g.n[0] - 2;
-  r.key_shift = 0;
-  while (((g.n[0] - 2) >> r.key_shift) >= 64) ++r.key_shift;
-  const size_t chunk = (size_t)64 * (K + KL);
-  const size_t rounds = (npts + chunk - 1) / chunk;
-  if (rounds > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-  r.rounds = (unsigned)rounds;
-  r.per_shard = (r.rounds + 7u) / 8u;
-  r.period = g.cfg.sweep_period > 0 ? (unsigned)g.cfg.sweep_period : 0u;
-  r.period_default = 2500;
-  r.gated = g.sweep_gated ? 1u : 0u;
-  r.stamps = nullptr;
-  r.work = static_cast<SweepWork*>(work);
-  const unsigned cus = (unsigned)(g.cfg.num_cus > 0 ? g.cfg.num_cus : 256);
-  unsigned blocks = cus;
-  const unsigned need = (r.rounds + (TH / 64) - 1) / (TH / 64);
-  if (blocks > need) blocks = need;
+  r.key_shift = sweep_key_shift(r.key_cells);
+  if (!sweep_schedule(r, g, npts, (size_t)64 * (K + KL), 2500, work)) return hipErrorInvalidValue;
+  const unsigned blocks = sweep_blocks(g, r.rounds, TH);
   const size_t lds = (size_t)SweepRoundsLds<T, 2, K, KL>::kWave * (TH / 64) + SweepRoundsLds<T, 2, K, KL>::kWorkgroup;
   auto launch = [&](auto kern, bool fma) -> hipError_t {
-    if (lds > 64 * 1024) {  // (per launch: the two flavours are two kernels, and the call is cheap beside a batch of this size)
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
     g.tag.set("k_linear2_sweep", {fma, K, KL, TH}, 0b0001u);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(TH), lds, stream, s);
     return hipGetLastError();
@@ -403,10 +381,7 @@ static hipError_t launch2_t(const GridDesc& g, const void* const* obs, void* out
 }
 
 hipError_t launch_linear2_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad, void* work, hipStream_t stream) {
-  if (g.method != kLinear || g.ndims != 2 || !g.bricks || !work || npts == 0) return hipErrorInvalidValue;
-  for (int d = 0; d < 2; ++d)
-    if (reinterpret_cast<uintptr_t>(obs[d]) % 16) return hipErrorInvalidValue;
-  if (reinterpret_cast<uintptr_t>(out) % 16) return hipErrorInvalidValue;
+  if (g.ndims != 2 || !g.bricks) return hipErrorInvalidValue;
   if (g.dtype == kF64) return launch2_t<double>(g, obs, out, npts, first_bad, work, stream);
   return launch2_t<float>(g, obs, out, npts, first_bad, work, stream);
 }

@@ -1,6 +1,5 @@
 // Host side of the sweep evaluation of 3-D multilinear batches (linear_sweep.h): when it applies,
 // which table it runs on, and the launcher.
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 
@@ -79,10 +78,7 @@ bool sweep_layout(const GridDesc& g, int* si, int* sj, int* cell) {
 }
 
 // 0 = never for this handle, 1 = not for this batch, 2 = yes.
-int sweep_applies(const GridDesc& g, size_t npts) {
-  if (g.method == kNearest) return nearest_sweep_applies(g, npts);  // 2-D / 3-D nearest neighbour: k_nearest.hip
-  if (g.method == kCubic) return cubic_sweep_applies(g, npts);  // 3-D multicubic: cubic_sweep.h
-  if (g.method == kLinear && g.ndims == 2) return linear2_sweep_applies(g, npts);  // 2-D multilinear: k_linear2_brick.hip
+int linear3_sweep_applies(const GridDesc& g, size_t npts) {
   if (!g.sweep_bricks || g.cfg.sweep == 0 || g.cfg.force_generic) return 0;
   if (g.sweep_table_bytes >= (1ull << 32)) return 0;
   // the rows' index arithmetic is 24-bit (linear_brick.h::brick_line_bytes24, div_small): axes shorter than 2^20, fewer than
@@ -119,16 +115,10 @@ static hipError_t go(const GridDesc& g, const SweepArgs<T>& s, unsigned blocks, 
   constexpr int K = sweep_rows<T, RECT, AXR>(), KL = sweep_parked<T, RECT, AXR>(), TH = kSweepThreads;
   auto kern = k_linear_sweep<T, RECT, FMA, SI, SJ, K, TH, AXR, false, CELL, KL>;
   const size_t lds = (size_t)SweepLds<T, K, KL>::kWave * (TH / 64) + SweepLds<T, K, KL>::kWorkgroup + ((RECT && AXR == 4 && s.b.ax.use_lds) ? (size_t)s.b.ax.image_bytes : 0);
-  static std::atomic<unsigned long long> opted{0};  // bit per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError();
-  if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || !((opted.load() >> dev) & 1ull))) {
-    // (the largest this instantiation ever asks for: its waves' regions + the axis image budget)
-    const size_t most = (size_t)SweepLds<T, K, KL>::kWave * (TH / 64) + SweepLds<T, K, KL>::kWorkgroup + (RECT && AXR == 4 ? kSweepAxisLds : 0);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) opted.fetch_or(1ull << dev);
-  }
+  // opted in to the largest this instantiation ever asks for (its waves' regions + the axis image budget): once per device
+  const size_t most = (size_t)SweepLds<T, K, KL>::kWave * (TH / 64) + SweepLds<T, K, KL>::kWorkgroup + (RECT && AXR == 4 ? kSweepAxisLds : 0);
+  hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), most);
+  if (e != hipSuccess) return e;
   g.tag.set("k_linear_sweep", {RECT, FMA, SI, SJ, K, TH, AXR, 0, CELL, KL, 0}, 0b00010000011u);  // (the last: ABL, measurement builds only)
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(TH), lds, stream, s);
   return hipGetLastError();
@@ -212,15 +202,7 @@ static hipError_t probe_t(const GridDesc& g, const void* const* obs, size_t npts
   p.seq = seq;
   for (int d = 0; d < N; ++d) {
     p.obs[d] = static_cast<const T*>(obs[d]);
-    if (g.kind == kRectilinear) {
-      const double span = g.bound_hi[d] - g.bound_lo[d];
-      p.start[d] = (T)g.bound_lo[d];
-      p.scale[d] = span > 0 ? (T)((double)(g.n[d] - 1) / span) : (T)0;
-    } else {
-      p.start[d] = (T)g.start[d];
-      p.scale[d] = (T)(1.0 / g.step[d]);
-    }
-    if (!(p.scale[d] > 0) || !(p.scale[d] < (T)1e30)) p.scale[d] = 0;
+    sweep_key(g, d, &p.start[d], &p.scale[d]);
     p.top[d] = g.n[d] - 2;
   }
   const int per_line = (int)(128 / sizeof(T));
@@ -258,7 +240,6 @@ template <typename T>
 static hipError_t launch_t(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
                            void* work, hipStream_t stream) {
   SweepArgs<T> s;
-  s.gated = g.sweep_gated ? 1u : 0u;
   BrickArgs<T, 3>& a = s.b;
   a.gate = nullptr;
   a.bricks = static_cast<const T*>(g.sweep_bricks);
@@ -284,40 +265,14 @@ static hipError_t launch_t(const GridDesc& g, const void* const* obs, void* out,
     if (axr == 0) axr = 4;  // axes longer than a wave: searched in the (LDS-staged) axis image
     (void)fill_axis_args<T, 3>(g, a.ax, false, /*records=*/axr == 4);
     if (a.ax.use_lds && a.ax.image_bytes > kSweepAxisLds) a.ax.use_lds = 0;
-    // the uniform grid over the leading axis' span (bound_lo / bound_hi are g[0] and g[n-1])
-    const double span = g.bound_hi[0] - g.bound_lo[0];
-    s.key_start = (T)g.bound_lo[0];
-    s.key_scale = span > 0 ? (T)((double)(g.n[0] - 1) / span) : (T)0;
-  } else {
-    s.key_start = (T)g.start[0];
-    s.key_scale = (T)(1.0 / g.step[0]);
   }
-  if (!(s.key_scale > 0) || !(s.key_scale < (T)1e30)) { s.key_scale = 0; }  // every point in bin 0: still correct
-  // regular grids: the correctly rounded reciprocals of the steps, and whether every step lies where the
-  // division-free forms of interpn_device.h::step_cell_fast are the reference's values
-  s.fastdiv = g.kind == kRectilinear ? 0u : 1u;
-  for (int d = 0; d < 3; ++d) {
-    const T st = (T)g.step[d];
-    const volatile T one = (T)1;   // (one IEEE division in T, at run time)
-    s.rstep[d] = g.kind == kRectilinear ? (T)0 : one / st;
-    const double mag = st < 0 ? -(double)st : (double)st;
-    if (!(mag >= StepCellRange<T>::lo && mag <= StepCellRange<T>::hi)) s.fastdiv = 0;  // (NaN, 0, infinities, far-out steps: the divide sequences)
-  }
-  s.key_shift = 0;
-  while (((g.n[0] - 2) >> s.key_shift) >= 64) ++s.key_shift;
+  sweep_key(g, 0, &s.key_start, &s.key_scale);
+  s.key_shift = sweep_key_shift(g.n[0] - 2);
+  step_reciprocals(g, s.rstep, &s.fastdiv);
   const size_t chunk = (size_t)64 * (g.kind == kRectilinear ? sweep_rows<T, true>() + sweep_parked<T, true>() : sweep_rows<T, false>() + sweep_parked<T, false>());
-  const size_t rounds = (npts + chunk - 1) / chunk;
-  if (rounds > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-  s.rounds = (unsigned)rounds;
-  s.per_shard = (s.rounds + 7u) / 8u;
-  s.period = g.cfg.sweep_period > 0 ? (unsigned)g.cfg.sweep_period : 0u;
-  s.period_default = 2600;  // 26 us: 0.9 x a round of 16 rows on a 64^3 f64 grid (the first launch through a scratch block; the kernel measures from then on)
-  s.work = static_cast<SweepWork*>(work);
-  s.stamps = nullptr;
-  const unsigned cus = (unsigned)(g.cfg.num_cus > 0 ? g.cfg.num_cus : 256);
-  unsigned blocks = cus;
-  const unsigned need = (s.rounds + (kSweepThreads / 64) - 1) / (kSweepThreads / 64);
-  if (blocks > need) blocks = need;
+  // 26 us: 0.9 x a round of 16 rows on a 64^3 f64 grid
+  if (!sweep_schedule(s, g, npts, chunk, 2600, work)) return hipErrorInvalidValue;
+  const unsigned blocks = sweep_blocks(g, s.rounds, kSweepThreads);
 #define SWEEP_KIND(RECT_, AXR_) (g.fma ? go_layout<T, RECT_, true, AXR_>(g, s, blocks, stream) : go_layout<T, RECT_, false, AXR_>(g, s, blocks, stream))
   switch (axr) {
     case 0: return SWEEP_KIND(false, 0);
@@ -330,15 +285,9 @@ static hipError_t launch_t(const GridDesc& g, const void* const* obs, void* out,
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_linear_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
-                               void* work, hipStream_t stream) {
-  if (g.method == kNearest) return launch_nearest_sweep(g, obs, out, npts, first_bad, work, stream);
-  if (g.method == kCubic) return launch_cubic_sweep(g, obs, out, npts, first_bad, work, stream);
-  if (g.method == kLinear && g.ndims == 2) return launch_linear2_sweep(g, obs, out, npts, first_bad, work, stream);
-  if (g.ndims != 3 || !g.sweep_bricks || !work || npts == 0) return hipErrorInvalidValue;
-  for (int d = 0; d < 3; ++d)
-    if (reinterpret_cast<uintptr_t>(obs[d]) % 16) return hipErrorInvalidValue;  // the caller checked (abi_sweep.hip)
-  if (reinterpret_cast<uintptr_t>(out) % 16) return hipErrorInvalidValue;
+hipError_t launch_linear3_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad,
+                                void* work, hipStream_t stream) {
+  if (g.ndims != 3 || !g.sweep_bricks) return hipErrorInvalidValue;
   if (g.dtype == kF64) return launch_t<double>(g, obs, out, npts, first_bad, work, stream);
   return launch_t<float>(g, obs, out, npts, first_bad, work, stream);
 }

@@ -2,7 +2,6 @@
 // src/nearest/rectilinear.rs:36-60, :193-262).  The same per-dimension index stage as the
 // multilinear kernels, then ONE gather per point: the node at origin + (dt <= 0.5 ? 0 : 1).
 // 64-bit indexing throughout (a single gather, nothing to save with 32-bit offsets).
-#include <atomic>
 #include <type_traits>
 
 #include "lane_axes.h"
@@ -280,7 +279,6 @@ static hipError_t launch_sweep_n(const GridDesc& g, const void* const* obs, void
   r.out = static_cast<T*>(out);
   s.first_bad = first_bad;
   r.npts = npts;
-  s.fastdiv = 1;
   unsigned long long acc = 1;
   for (int d = N - 1; d >= 0; --d) {
     r.obs[d] = static_cast<const T*>(obs[d]);
@@ -290,37 +288,17 @@ static hipError_t launch_sweep_n(const GridDesc& g, const void* const* obs, void
     s.n[d] = g.n[d];
     s.stride[d] = acc;
     acc *= (unsigned long long)g.n[d];
-    const volatile T one = (T)1;
-    s.rstep[d] = one / (T)g.step[d];
-    const double mag = g.step[d] < 0 ? -g.step[d] : g.step[d];
-    if (!(mag >= StepCellRange<T>::lo && mag <= StepCellRange<T>::hi)) s.fastdiv = 0;
   }
-  r.key_start = (T)g.start[0];
-  r.key_scale = (T)(1.0 / g.step[0]);
-  if (!(r.key_scale > 0) || !(r.key_scale < (T)1e30)) r.key_scale = 0;
+  step_reciprocals(g, s.rstep, &s.fastdiv);
+  sweep_key(g, 0, &r.key_start, &r.key_scale);
   r.key_cells = g.n[0] - 2;
-  r.key_shift = 0;
-  while (((g.n[0] - 2) >> r.key_shift) >= 64) ++r.key_shift;
-  const size_t chunk = (size_t)64 * (K + KL);
-  const size_t rounds = (npts + chunk - 1) / chunk;
-  if (rounds > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-  r.rounds = (unsigned)rounds;
-  r.per_shard = (r.rounds + 7u) / 8u;
-  r.period = g.cfg.sweep_period > 0 ? (unsigned)g.cfg.sweep_period : 0u;
-  r.period_default = 2000;
-  r.gated = g.sweep_gated ? 1u : 0u;
-  r.stamps = nullptr;
-  r.work = static_cast<SweepWork*>(work);
-  const unsigned cus = (unsigned)(g.cfg.num_cus > 0 ? g.cfg.num_cus : 256);
-  unsigned blocks = cus;
-  const unsigned need = (r.rounds + (TH / 64) - 1) / (TH / 64);
-  if (blocks > need) blocks = need;
+  r.key_shift = sweep_key_shift(r.key_cells);
+  if (!sweep_schedule(r, g, npts, (size_t)64 * (K + KL), 2000, work)) return hipErrorInvalidValue;
+  const unsigned blocks = sweep_blocks(g, r.rounds, TH);
   const size_t lds = (size_t)SweepRoundsLds<T, N, K, KL>::kWave * (TH / 64) + SweepRoundsLds<T, N, K, KL>::kWorkgroup;
   auto launch = [&](auto kern, bool fma) -> hipError_t {
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
     g.tag.set("k_nearest_sweep", {N, fma, K, KL, TH}, 0b00010u);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(TH), lds, stream, s);
     return hipGetLastError();
@@ -329,10 +307,6 @@ static hipError_t launch_sweep_n(const GridDesc& g, const void* const* obs, void
 }
 
 hipError_t launch_nearest_sweep(const GridDesc& g, const void* const* obs, void* out, size_t npts, unsigned long long* first_bad, void* work, hipStream_t stream) {
-  if (g.method != kNearest || !work || npts == 0) return hipErrorInvalidValue;
-  for (int d = 0; d < g.ndims; ++d)
-    if (reinterpret_cast<uintptr_t>(obs[d]) % 16) return hipErrorInvalidValue;
-  if (reinterpret_cast<uintptr_t>(out) % 16) return hipErrorInvalidValue;
   if (g.ndims == 2) return g.dtype == kF64 ? launch_sweep_n<double, 2>(g, obs, out, npts, first_bad, work, stream) : launch_sweep_n<float, 2>(g, obs, out, npts, first_bad, work, stream);
   if (g.ndims == 3) return g.dtype == kF64 ? launch_sweep_n<double, 3>(g, obs, out, npts, first_bad, work, stream) : launch_sweep_n<float, 3>(g, obs, out, npts, first_bad, work, stream);
   return hipErrorInvalidValue;

@@ -89,7 +89,7 @@ __device__ __forceinline__ unsigned div_small(unsigned x) {
 // f32 2 x 4 x 4 bricks) — brick_piece<T, 1, 1, CELL>(nbj, nbk, i, j, bk * ELEMS + (k - bk * SK), 0, 0) * sizeof(T) with
 // 24-bit multiplies (v_mul_u32_u24 / v_mad_u32_u24: full rate, where v_mul_lo_u32, v_mul_hi_u32 and v_mad_u64_u32 run at a
 // quarter of it: four of them per row were 16 of a sweep row's ~115 issue slots).  The host takes the sweep kernels only
-// where i * nbj + j, nbk < 2^24 and every axis is shorter than 2^20 (k_linear_sweep.hip::sweep_applies).
+// where i * nbj + j, nbk < 2^24 and every axis is shorter than 2^20 (k_linear_sweep.hip::linear3_sweep_applies).
 // a * b + c on 24-bit operands, b wave-uniform (the compiler, left to itself, turns mul24 + add back into v_mad_u64_u32)
 __device__ __forceinline__ unsigned mad24_vsv(unsigned a, unsigned b_uniform, unsigned c) {
   unsigned r;

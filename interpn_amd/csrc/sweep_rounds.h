@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "interpn_device.h"
+#include "interpn_host.h"
 
 namespace interpn {
 
@@ -317,6 +318,72 @@ __device__ __forceinline__ void sweep_rounds(const SweepRounds<T, N>& sr, unsign
       }
     }
   }
+}
+
+// ---- host side: the arguments every sweep launcher fills the same way (SweepRounds above, linear_sweep.h's SweepArgs) ----
+
+// The sort key along dimension `dim`: (x - start) * scale ~ the cell index (a locality hint, it need not be the exact cell;
+// rectilinear grids: the uniform grid over the axis' span, bound_lo / bound_hi being g[0] and g[n-1]).  A scale that is not
+// positive and finite puts every point in bin 0: still correct.
+template <typename T>
+inline void sweep_key(const GridDesc& g, int dim, T* start, T* scale) {
+  if (g.kind == kRectilinear) {
+    const double span = g.bound_hi[dim] - g.bound_lo[dim];
+    *start = (T)g.bound_lo[dim];
+    *scale = span > 0 ? (T)((double)(g.n[dim] - 1) / span) : (T)0;
+  } else {
+    *start = (T)g.start[dim];
+    *scale = (T)(1.0 / g.step[dim]);
+  }
+  if (!(*scale > 0) || !(*scale < (T)1e30)) *scale = 0;
+}
+
+// key_shift: the cell index along the key's dimension (0 .. cells) >> key_shift < 64 bins
+inline int sweep_key_shift(int cells) {
+  int shift = 0;
+  while ((cells >> shift) >= 64) ++shift;
+  return shift;
+}
+
+// Regular grids: the correctly rounded reciprocals of the steps (one IEEE division in T, at run time), and whether every step
+// lies where the division-free forms of interpn_device.h (step_cell_fast, divide_fast) are the reference's values — tested on
+// the step rounded to T, the value the kernels divide by (StepCellRange<T>; NaN, 0, infinities, far-out steps: the divide
+// sequences).  Rectilinear grids: neither.
+template <typename T, int N>
+inline void step_reciprocals(const GridDesc& g, T (&rstep)[N], unsigned* fastdiv) {
+  *fastdiv = g.kind == kRectilinear ? 0u : 1u;
+  for (int d = 0; d < N; ++d) {
+    const T st = (T)g.step[d];
+    const volatile T one = (T)1;
+    rstep[d] = g.kind == kRectilinear ? (T)0 : one / st;
+    const double mag = st < 0 ? -(double)st : (double)st;
+    if (!(mag >= StepCellRange<T>::lo && mag <= StepCellRange<T>::hi)) *fastdiv = 0;
+  }
+}
+
+// The schedule of a launch of `npts` points in rounds of `round_points` (64 x the rows of a wave): eight shards of rounds taken
+// on demand, the gate of an automatic launch, and the period — option sweep_period, else what the last launch through `work`
+// measured, else `period_default` (ticks of 10 ns: the family's guess for the first launch through a scratch block).  A: a
+// SweepRounds or linear_sweep.h's SweepArgs.  false: more rounds than the kernels count.
+template <typename A>
+inline bool sweep_schedule(A& s, const GridDesc& g, size_t npts, size_t round_points, unsigned period_default, void* work) {
+  const size_t rounds = (npts + round_points - 1) / round_points;
+  if (rounds > 0xFFFFFFF0ull) return false;
+  s.rounds = (unsigned)rounds;
+  s.per_shard = (s.rounds + 7u) / 8u;
+  s.period = g.cfg.sweep_period > 0 ? (unsigned)g.cfg.sweep_period : 0u;
+  s.period_default = period_default;
+  s.gated = g.sweep_gated ? 1u : 0u;
+  s.work = static_cast<SweepWork*>(work);
+  s.stamps = nullptr;
+  return true;
+}
+
+// Workgroups of `threads` for a launch of `rounds`: one per CU, fewer where the rounds do not give every wave one.
+inline unsigned sweep_blocks(const GridDesc& g, unsigned rounds, int threads) {
+  const unsigned cus = (unsigned)(g.cfg.num_cus > 0 ? g.cfg.num_cus : 256);
+  const unsigned need = (rounds + (unsigned)(threads / 64) - 1) / (unsigned)(threads / 64);
+  return cus < need ? cus : need;
 }
 
 }  // namespace interpn
