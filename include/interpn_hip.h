@@ -118,6 +118,8 @@ typedef enum interpn_hip_status {
   INTERPN_HIP_ERR_TOO_MANY_DIMS = 8,     /* "Dimension exceeds maximum (8). Use interpolator struct directly for higher dimensions." */
   INTERPN_HIP_ERR_REFERENCE_PANIC = 9,   /* the reference would panic here */
   INTERPN_HIP_ERR_TOO_MANY_DIMS_6 = 10,  /* "Dimension exceeds maximum (6)."           nearest/regular.rs:97 */
+  INTERPN_HIP_ERR_LENGTH_MISMATCH = 11,  /* "Length mismatch"                           one_dim/mod.rs:53, :150 */
+  INTERPN_HIP_ERR_UNREPRESENTABLE_NUMBER = 12, /* "Unrepresentable number"              one_dim/mod.rs:111 */
   /* statuses of this implementation */
   INTERPN_HIP_ERR_INVALID_ARGUMENT = 32, /* null pointer, unknown enum value, dtype mismatch */
   INTERPN_HIP_ERR_UNSUPPORTED = 33,      /* axis longer than 2^31-257 points (f32: 2^24) */
@@ -133,6 +135,14 @@ enum { INTERPN_HIP_LINEAR = 0, INTERPN_HIP_CUBIC = 1, INTERPN_HIP_NEAREST = 2 };
  * threads.  Also readable / writable as the per-handle option "fma" (not while evaluations of the
  * same handle are being enqueued by another thread). */
 enum { INTERPN_HIP_FLAVOUR_FMA = 0x100, INTERPN_HIP_FLAVOUR_NO_FMA = 0x200 };
+/* interpn::one_dim (src/one_dim/), for interpn_hip_create_grid1d_* only; the flavour bits OR into them as above. */
+enum {
+  INTERPN_HIP_LINEAR_1D = 16,           /* one_dim::linear::Linear1D          one_dim/linear.rs:26-37 */
+  INTERPN_HIP_LINEAR_HOLD_LAST_1D = 17, /* one_dim::linear::LinearHoldLast1D  one_dim/linear.rs:60-85 */
+  INTERPN_HIP_LEFT_1D = 18,             /* one_dim::hold::Left1D              one_dim/hold.rs:26-38 */
+  INTERPN_HIP_RIGHT_1D = 19,            /* one_dim::hold::Right1D             one_dim/hold.rs:61-73 */
+  INTERPN_HIP_NEAREST_1D = 20           /* one_dim::hold::Nearest1D           one_dim/hold.rs:94-107 */
+};
 enum { INTERPN_HIP_MEM_HOST = 0, INTERPN_HIP_MEM_DEVICE = 1 }; /* where a buffer lives */
 
 const char* interpn_hip_strerror(int status);
@@ -228,6 +238,35 @@ typedef struct interpn_hip_interp interpn_hip_interp;
 
 INTERPN_HIP_DECLARE_CREATE(double, f64)
 INTERPN_HIP_DECLARE_CREATE(float, f32)
+
+/* ------------------------------------------------------------------------------------------
+ * interpn::one_dim — the counterpart of RegularGrid1D::new(start, step, vals) (one_dim/mod.rs:86-95) or
+ * RectilinearGrid1D::new(grid, vals) (one_dim/mod.rs:148-154) wrapped in one of the five interpolators
+ * (`method` = INTERPN_HIP_*_1D [| INTERPN_HIP_FLAVOUR_*]).  Every check runs before any device work:
+ *   regular      nvals < 2: INTERPN_HIP_ERR_REFERENCE_PANIC (the reference panics at the first evaluated point, or in
+ *                `new` for an empty slice); no check of `step` (zero, negative, NaN are accepted);
+ *                stop = start + step * T(nvals - 1), two roundings in T
+ *   rectilinear  ngrid != nvals or ngrid < 2: INTERPN_HIP_ERR_LENGTH_MISMATCH; no sortedness check
+ *   both         more than 2^31 - 257 values, or a rectilinear axis of 4 GiB or more (f64: 2^29 values, f32: 2^30):
+ *                INTERPN_HIP_ERR_UNSUPPORTED
+ * The handle has ndims = 1 and is evaluated by the existing entry points (eval_host, eval_device(_ex), the sharded
+ * forms, finish, replicate), which mirror Interp1D::eval (one_dim/mod.rs:51-61): nobs != 1 is
+ * INTERPN_HIP_ERR_INVALID_ARGUMENT, obs_lens[0] != nout INTERPN_HIP_ERR_LENGTH_MISMATCH, and a point whose cell index
+ * does not convert to isize (regular grids: NaN, +-inf, |(x - start) / step| >= 2^63) is
+ * INTERPN_HIP_ERR_UNREPRESENTABLE_NUMBER with the abort-at-first-bad-point contract described above (where the other
+ * handles say INTERPN_HIP_ERR_UNREPRESENTABLE).  Rectilinear grids never fail a point.  interpn_hip_check_bounds_device
+ * returns INTERPN_HIP_ERR_INVALID_ARGUMENT (the reference has no bounds check for one_dim); interpn_hip_table_bytes
+ * reports the per-cell record table (k_one_dim.hip).
+ * ---------------------------------------------------------------------------------------- */
+#define INTERPN_HIP_DECLARE_CREATE_1D(T, SUFFIX)                                                                  \
+  int interpn_hip_create_grid1d_regular_##SUFFIX(int method, T start, T step, const T* vals, size_t nvals,        \
+                                                 int vals_mem, int device, interpn_hip_interp** handle);          \
+  int interpn_hip_create_grid1d_rectilinear_##SUFFIX(int method, const T* grid, size_t ngrid, const T* vals,      \
+                                                     size_t nvals, int vals_mem, int device,                      \
+                                                     interpn_hip_interp** handle);
+
+INTERPN_HIP_DECLARE_CREATE_1D(double, f64)
+INTERPN_HIP_DECLARE_CREATE_1D(float, f32)
 
 /* Clone `src` onto `device` (-1 = current) of the same process: the grid (and the axes of a
  * rectilinear grid) travels device to device (hipMemcpyPeer, i.e. xGMI between the GPUs of one

@@ -17,6 +17,13 @@
 //   interpn::multicubic::rectilinear::*         multicubic/rectilinear.rs:54,111,123,193,237,265
 //   interpn::nearest::{regular,rectilinear}::*  nearest/regular.rs:41,108,163,206,234; rectilinear.rs:39,73,124,159,193
 //   interpn::utils::{linspace, meshgrid}        utils.rs:8,17     interpn_hip::utils::{linspace, meshgrid}
+//   interpn::one_dim::{Extrap, RegularGrid1D, RectilinearGrid1D}  one_dim/mod.rs:12,78,142   interpn_hip::one_dim::...
+//   RegularGrid1D::new(start, step, vals)       one_dim/mod.rs:86     RegularGrid1D<T>::new_        (borrows `vals`)
+//   RectilinearGrid1D::new(grid, vals)          one_dim/mod.rs:148    RectilinearGrid1D<T>::new_    (borrows both)
+//   one_dim::hold::{Left1D, Right1D, Nearest1D}::new       hold.rs:13,48,84   one_dim::hold::{Left1D, Right1D, Nearest1D}<G>::new_
+//   one_dim::linear::{Linear1D, LinearHoldLast1D}::new     linear.rs:14,48    one_dim::linear::{Linear1D, LinearHoldLast1D}<G>::new_
+//   Interp1D::eval_one / eval / eval_alloc      one_dim/mod.rs:45,51,69   ::eval_one / ::eval / ::eval_alloc
+//   (re-exported at the crate root, lib.rs:102-105: interpn_hip::{RegularGrid1D, ..., LinearHoldLast1D})
 //
 //   &[T] -> Slice<T> (pointer + length, implicit from std::vector / std::array / C arrays),
 //   &mut [T] -> SliceMut<T>, &[&[T]] -> Slice<Slice<T>>,
@@ -543,6 +550,116 @@ using multicubic::MulticubicRectilinear;
 using multicubic::MulticubicRegular;
 using nearest::NearestRectilinear;
 using nearest::NearestRegular;
+
+// ---------------------------------------------------------------------------------------------
+// interpn::one_dim (src/one_dim/).  The grids borrow their slices like the Rust structs; an interpolator owns a device
+// handle made from them (move-only), so the slices may be freed after `new_`.  Rust's `Left1D::new(grid)` cannot fail;
+// here `new_` returns a Result because it creates the handle: no device, out of memory, or
+// INTERPN_HIP_ERR_REFERENCE_PANIC for a regular grid of fewer than two values (the reference panics at the first point).
+namespace one_dim {
+
+enum class Extrap { Inside, OutsideLow, OutsideHigh };  // one_dim/mod.rs:12-16 (what `index` reports; not evaluated here)
+
+template <class T>
+class RegularGrid1D {
+ public:
+  using value_type = T;
+  // one_dim/mod.rs:86-95: no validation of `step`; the conversion of vals.len() - 1 cannot fail for f32 / f64
+  static Result<RegularGrid1D> new_(T start, T step, Slice<T> vals) { return Result<RegularGrid1D>::Ok(RegularGrid1D(start, step, vals)); }
+  int create(int method, int device, interpn_hip_interp** h) const {
+    if constexpr (std::is_same<T, double>::value)
+      return interpn_hip_create_grid1d_regular_f64(method, start_, step_, vals_.ptr, vals_.len(), INTERPN_HIP_MEM_HOST, device, h);
+    else
+      return interpn_hip_create_grid1d_regular_f32(method, start_, step_, vals_.ptr, vals_.len(), INTERPN_HIP_MEM_HOST, device, h);
+  }
+  RegularGrid1D() = default;
+
+ private:
+  RegularGrid1D(T start, T step, Slice<T> vals) : start_(start), step_(step), vals_(vals) {}
+  T start_ = T(), step_ = T();
+  Slice<T> vals_;
+};
+
+template <class T>
+class RectilinearGrid1D {
+ public:
+  using value_type = T;
+  // one_dim/mod.rs:148-154: "Length mismatch" unless grid and vals have the same length, at least 2; no sortedness check
+  static Result<RectilinearGrid1D> new_(Slice<T> grid, Slice<T> vals) {
+    if (grid.len() != vals.len() || grid.len() < 2) return Result<RectilinearGrid1D>::Err(INTERPN_HIP_ERR_LENGTH_MISMATCH);
+    return Result<RectilinearGrid1D>::Ok(RectilinearGrid1D(grid, vals));
+  }
+  int create(int method, int device, interpn_hip_interp** h) const {
+    if constexpr (std::is_same<T, double>::value)
+      return interpn_hip_create_grid1d_rectilinear_f64(method, grid_.ptr, grid_.len(), vals_.ptr, vals_.len(), INTERPN_HIP_MEM_HOST,
+                                                       device, h);
+    else
+      return interpn_hip_create_grid1d_rectilinear_f32(method, grid_.ptr, grid_.len(), vals_.ptr, vals_.len(), INTERPN_HIP_MEM_HOST,
+                                                       device, h);
+  }
+  RectilinearGrid1D() = default;
+
+ private:
+  RectilinearGrid1D(Slice<T> grid, Slice<T> vals) : grid_(grid), vals_(vals) {}
+  Slice<T> grid_, vals_;
+};
+
+namespace detail {
+
+// Interp1D (one_dim/mod.rs:41-74) over a device handle; METHOD = INTERPN_HIP_*_1D
+template <class G, int METHOD>
+class Interp1D : public interpn_hip::detail::Handle<typename G::value_type, 1> {
+  using T = typename G::value_type;
+  using Base = interpn_hip::detail::Handle<T, 1>;
+
+ public:
+  Interp1D() = default;
+  static Result<Interp1D> new_(const G& grid, int device = -1) {
+    interpn_hip_interp* h = nullptr;
+    const int st = grid.create(METHOD | interpn_hip::detail::kFlavour, device, &h);
+    return st == INTERPN_HIP_OK ? Result<Interp1D>::Ok(Interp1D(h)) : Result<Interp1D>::Err(st);
+  }
+  // one_dim/mod.rs:51-61: "Length mismatch" unless locs and out have the same length; stops at the first point that
+  // fails ("Unrepresentable number", regular grids) with out[0..i) written and out[i..] untouched
+  Result<void> eval(Slice<T> locs, SliceMut<T> out) const {
+    const void* p = locs.ptr;
+    const std::size_t n = locs.len();
+    return Result<void>::from(interpn_hip_eval_host(this->h_, &p, &n, 1, out.ptr, out.len()));
+  }
+  Result<T> eval_one(T loc) const { return this->interp_one({loc}); }
+  Result<std::vector<T>> eval_alloc(Slice<T> locs) const {  // one_dim/mod.rs:67-73
+    std::vector<T> out(locs.len(), T());
+    Result<void> r = eval(locs, SliceMut<T>(out));
+    return r.is_ok() ? Result<std::vector<T>>::Ok(std::move(out)) : Result<std::vector<T>>::Err(r.status());
+  }
+
+ private:
+  explicit Interp1D(interpn_hip_interp* h) : Base(h) {}
+};
+
+}  // namespace detail
+
+namespace hold {
+template <class G> using Left1D = detail::Interp1D<G, INTERPN_HIP_LEFT_1D>;        // one_dim/hold.rs:8-39
+template <class G> using Right1D = detail::Interp1D<G, INTERPN_HIP_RIGHT_1D>;      // one_dim/hold.rs:43-75
+template <class G> using Nearest1D = detail::Interp1D<G, INTERPN_HIP_NEAREST_1D>;  // one_dim/hold.rs:79-108
+}  // namespace hold
+
+namespace linear {
+template <class G> using Linear1D = detail::Interp1D<G, INTERPN_HIP_LINEAR_1D>;                  // one_dim/linear.rs:9-38
+template <class G> using LinearHoldLast1D = detail::Interp1D<G, INTERPN_HIP_LINEAR_HOLD_LAST_1D>;  // one_dim/linear.rs:43-86
+}  // namespace linear
+
+}  // namespace one_dim
+
+// lib.rs:102-105
+using one_dim::RectilinearGrid1D;
+using one_dim::RegularGrid1D;
+using one_dim::hold::Left1D;
+using one_dim::hold::Nearest1D;
+using one_dim::hold::Right1D;
+using one_dim::linear::Linear1D;
+using one_dim::linear::LinearHoldLast1D;
 
 // ---------------------------------------------------------------------------------------------
 namespace utils {

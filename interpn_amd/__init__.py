@@ -13,7 +13,7 @@ from typing import Literal
 
 import numpy as np
 
-from . import _lib, raw
+from . import _lib, one_dim, raw
 from .classes import (MulticubicRectilinear, MulticubicRegular, MultilinearRectilinear, MultilinearRegular,
                       NearestRectilinear, NearestRegular)
 from .handle import Interpolator, eval_device_sharded, eval_host_sharded
@@ -31,6 +31,7 @@ def trim(device: int = -1) -> int:
 
 
 __all__ = [
+    "one_dim",
     "trim",
     "eval_host_sharded",
     "eval_device_sharded",

@@ -20,10 +20,15 @@ ERR_DIM_MISMATCH = 1
 ERR_UNREPRESENTABLE = 7
 ERR_REFERENCE_PANIC = 9
 ERR_TOO_MANY_DIMS_6 = 10
+ERR_LENGTH_MISMATCH = 11          # "Length mismatch" (one_dim)
+ERR_UNREPRESENTABLE_NUMBER = 12   # "Unrepresentable number" (one_dim, regular grids)
+UNREPRESENTABLE = (ERR_UNREPRESENTABLE, ERR_UNREPRESENTABLE_NUMBER)  # statuses that carry a first failing index
 ERR_INVALID_ARGUMENT = 32
 
 LINEAR, CUBIC, NEAREST = 0, 1, 2
 METHODS = {"linear": LINEAR, "cubic": CUBIC, "nearest": NEAREST}
+# interpn::one_dim (interpn_hip_create_grid1d_*)
+METHODS_1D = {"Linear1D": 16, "LinearHoldLast1D": 17, "Left1D": 18, "Right1D": 19, "Nearest1D": 20}
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAVOUR_FMA, FLAVOUR_NO_FMA = 0x100, 0x200  # OR-ed into `method` of interpn_hip_create_*
 PATH_IN_PLACE, PATH_BINNED, PATH_SWEEP = 0, 1, 2
@@ -110,6 +115,10 @@ def load() -> ctypes.CDLL:
             POINTER(c_void_p)]
         getattr(lib, f"interpn_hip_create_rectilinear_{sfx}").argtypes = [
             c_int, pp, sz, c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, POINTER(c_void_p)]
+        getattr(lib, f"interpn_hip_create_grid1d_regular_{sfx}").argtypes = [
+            c_int, ct, ct, c_void_p, c_size_t, c_int, c_int, POINTER(c_void_p)]
+        getattr(lib, f"interpn_hip_create_grid1d_rectilinear_{sfx}").argtypes = [
+            c_int, p, c_size_t, c_void_p, c_size_t, c_int, c_int, POINTER(c_void_p)]
         getattr(lib, f"interpn_hip_check_bounds_regular_{sfx}").argtypes = [
             sz, c_size_t, p, c_size_t, p, c_size_t, pp, sz, c_size_t, ct, POINTER(c_uint8), c_size_t]
         getattr(lib, f"interpn_hip_check_bounds_rectilinear_{sfx}").argtypes = [
@@ -154,7 +163,7 @@ def raise_for_status(status: int) -> None:
     if status == OK:
         return
     msg = strerror(status)
-    if status < ERR_REFERENCE_PANIC or status == ERR_TOO_MANY_DIMS_6:
+    if status < ERR_REFERENCE_PANIC or status in (ERR_TOO_MANY_DIMS_6, ERR_LENGTH_MISMATCH, ERR_UNREPRESENTABLE_NUMBER):
         raise AssertionError(msg)
     if status == ERR_REFERENCE_PANIC:
         raise ReferencePanic(msg)

@@ -51,6 +51,7 @@ extern "C" {
 int interpn_hip_check_bounds_device(interpn_hip_interp* h, const void* const* obs, size_t nobs, size_t npoints,
                                     double atol, uint8_t* out, size_t nout, void* stream) {
   if (!h || (!obs && nobs)) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+  if (is_one_dim(h->desc.method)) return INTERPN_HIP_ERR_INVALID_ARGUMENT;  // one_dim has no bounds check
   const size_t ndims = (size_t)h->desc.ndims;
   if (!(nobs == ndims && nout == ndims)) return INTERPN_HIP_ERR_DIM_MISMATCH;  // regular.rs:153-156
   if (!out) return INTERPN_HIP_ERR_INVALID_ARGUMENT;

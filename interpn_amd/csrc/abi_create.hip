@@ -320,6 +320,104 @@ int create_rectilinear(int method, const T* const* grids, const size_t* grid_len
   return INTERPN_HIP_OK;
 }
 
+// interpn::one_dim: RegularGrid1D::new / RectilinearGrid1D::new (one_dim/mod.rs:86-95, :148-154) plus the interpolator.
+// Every check runs before any device work.  The cell records are built by finish_create -> maybe_build_bricks.
+template <typename T>
+int create_one_dim(int method, int kind, T start, T step, const T* grid, size_t ngrid, const T* vals, size_t nvals,
+                   int vals_mem, int device, interpn_hip_interp** handle) {
+  if (!handle) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+  *handle = nullptr;
+  const int flavour = method & (INTERPN_HIP_FLAVOUR_FMA | INTERPN_HIP_FLAVOUR_NO_FMA);
+  if (flavour == (INTERPN_HIP_FLAVOUR_FMA | INTERPN_HIP_FLAVOUR_NO_FMA)) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+  method &= ~(INTERPN_HIP_FLAVOUR_FMA | INTERPN_HIP_FLAVOUR_NO_FMA);
+  if (!is_one_dim(method)) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+  if (vals_mem != INTERPN_HIP_MEM_HOST && vals_mem != INTERPN_HIP_MEM_DEVICE) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+  if (kind == kRegular) {
+    // vals.len() - 1 underflows in `new` for an empty slice (a panic in a debug build), and with one value the first
+    // evaluated point panics at (vals.len() - 2) (one_dim/mod.rs:88, :113)
+    if (nvals < 2) return INTERPN_HIP_ERR_REFERENCE_PANIC;
+  } else {
+    if (ngrid != nvals || ngrid < 2) return INTERPN_HIP_ERR_LENGTH_MISMATCH;  // one_dim/mod.rs:149-150
+    if (!grid) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+  }
+  if (!vals) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+  if (nvals > (size_t)2147483391u) return INTERPN_HIP_ERR_UNSUPPORTED;  // cell indices are 32-bit
+  // the coordinates of a rectilinear axis are one allocation whose size GridDesc::axis_alloc_bytes holds in 32 bits
+  if (kind == kRectilinear && ngrid * sizeof(T) > (size_t)0xFFFFFFFFu) return INTERPN_HIP_ERR_UNSUPPORTED;
+  int dev;
+  int st = resolve_device(device, &dev);
+  if (st) return st;
+  DeviceGuard guard(dev);
+  if (!guard.ok()) return INTERPN_HIP_ERR_NO_DEVICE;
+  interpn_hip_interp* h = new (std::nothrow) interpn_hip_interp();
+  if (!h) return INTERPN_HIP_ERR_OUT_OF_MEMORY;
+  h->device = dev;
+  GridDesc& g = h->desc;
+  g.method = method;
+  g.kind = kind;
+  g.dtype = sizeof(T) == 8 ? kF64 : kF32;
+  g.ndims = 1;
+  g.fma = flavour == INTERPN_HIP_FLAVOUR_FMA ? 1 : (flavour == INTERPN_HIP_FLAVOUR_NO_FMA ? 0 : g_fma.load());
+  g.unrep_status = INTERPN_HIP_ERR_UNREPRESENTABLE_NUMBER;
+  g.n[0] = (int)nvals;
+  g.grid_total = nvals;
+  const size_t rec_bytes = (one_dim_record_bytes(g) + 15) & ~(size_t)15;
+  if (kind == kRegular) {
+    const T last = (T)(nvals - 1);     // <T as NumCast>::from(vals.len() - 1): rounds in f32 beyond 2^24
+    const T stop = start + step * last;  // one_dim/mod.rs:87-88, two roundings
+    g.od_start = (double)start;
+    g.od_step = (double)step;
+    g.od_stop = (double)stop;
+    g.start[0] = (double)start;
+    g.step[0] = (double)step;
+    // the divide-free cell index (interpn_device.h::floor_quotient_fast) for the steps it is proven for
+    const double lo = sizeof(T) == 8 ? 0x1p-128 : 0x1p-16, hi = sizeof(T) == 8 ? 0x1p128 : 0x1p16;  // StepCellRange<T>
+    const bool fast = (double)step >= lo && (double)step <= hi;
+    g.od_fast = fast ? 1 : 0;
+    g.od_rstep = fast ? (double)((T)1 / step) : 0.0;
+    g.od_table_bytes = rec_bytes;
+  } else {
+    const size_t n = ngrid;
+    g.bound_lo[0] = (double)grid[0];
+    g.bound_hi[0] = (double)grid[n - 1];
+    // bucket table over [g[0], g[n-1]] for strictly increasing finite axes (interpn_device.h::axis_partition_point);
+    // otherwise the std probe sequence, like the reference on an unsorted slice
+    bool sorted = true;
+    for (size_t k = 0; k + 1 < n && sorted; ++k) sorted = grid[k + 1] > grid[k];
+    sorted = sorted && std::isfinite((double)grid[0]) && std::isfinite((double)grid[n - 1]);
+    const double span = (double)grid[n - 1] - (double)grid[0];
+    int M = 0;
+    if (sorted && span > 0 && std::isfinite(span) && n <= ((size_t)1 << 28)) M = (int)(2 * n);
+    double scale = M ? (double)(T)((double)M / span) : 0.0;
+    if (M && !(scale > 0 && std::isfinite(scale))) { M = 0; scale = 0.0; }
+    g.od_M = M;
+    g.od_g0 = (double)grid[0];
+    g.od_scale = scale;
+    g.od_g_off = rec_bytes;
+    g.od_tab_off = g.od_g_off + ((n * sizeof(T) + 15) & ~(size_t)15);
+    g.od_table_bytes = g.od_tab_off + (M ? (((size_t)M + 1) * sizeof(unsigned) + 15) & ~(size_t)15 : 0);
+    // the coordinates as the handle's axis image (what interpn_hip_replicate copies device to device)
+    g.axis_alloc_bytes = (unsigned)(n * sizeof(T));  // < 4 GiB, checked above
+    hipError_t e = pool_alloc(h->device, &h->grids_owned, n * sizeof(T));
+    if (e == hipSuccess) e = hipMemcpy(h->grids_owned, grid, n * sizeof(T), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      interpn_hip_destroy(h);
+      return hip_fail(e);
+    }
+    g.axis_image = h->grids_owned;
+    g.grid[0] = h->grids_owned;
+  }
+  st = finish_create(h, vals, nvals, sizeof(T), vals_mem);
+  if (st) {
+    interpn_hip_destroy(h);
+    return st;
+  }
+  *handle = h;
+  return INTERPN_HIP_OK;
+}
+
+template int create_one_dim<double>(int, int, double, double, const double*, size_t, const double*, size_t, int, int, interpn_hip_interp**);
+template int create_one_dim<float>(int, int, float, float, const float*, size_t, const float*, size_t, int, int, interpn_hip_interp**);
 
 template int create_regular<double>(int, const size_t*, size_t, const double*, size_t, const double*, size_t, const double*, size_t, int, int, int, interpn_hip_interp**);
 template int create_regular<float>(int, const size_t*, size_t, const float*, size_t, const float*, size_t, const float*, size_t, int, int, int, interpn_hip_interp**);
@@ -344,6 +442,8 @@ const char* interpn_hip_strerror(int status) {
     case INTERPN_HIP_ERR_TOO_MANY_DIMS:
       return "Dimension exceeds maximum (8). Use interpolator struct directly for higher dimensions.";
     case INTERPN_HIP_ERR_TOO_MANY_DIMS_6: return "Dimension exceeds maximum (6).";
+    case INTERPN_HIP_ERR_LENGTH_MISMATCH: return "Length mismatch";
+    case INTERPN_HIP_ERR_UNREPRESENTABLE_NUMBER: return "Unrepresentable number";
     case INTERPN_HIP_ERR_REFERENCE_PANIC: return "the reference implementation panics on this input (slice length mismatch or integer overflow)";
     case INTERPN_HIP_ERR_INVALID_ARGUMENT: return "invalid argument";
     case INTERPN_HIP_ERR_UNSUPPORTED: return "grid axis too long for the device kernels";
@@ -393,6 +493,20 @@ int interpn_hip_trim(int device, size_t* freed_bytes) {
   }
 DEFINE_CREATE(double, f64)
 DEFINE_CREATE(float, f32)
+
+#define DEFINE_CREATE_1D(T, SUFFIX)                                                                           \
+  int interpn_hip_create_grid1d_regular_##SUFFIX(int method, T start, T step, const T* vals, size_t nvals,   \
+                                                 int vals_mem, int device, interpn_hip_interp** handle) {    \
+    return create_one_dim<T>(method, kRegular, start, step, nullptr, 0, vals, nvals, vals_mem, device, handle); \
+  }                                                                                                           \
+  int interpn_hip_create_grid1d_rectilinear_##SUFFIX(int method, const T* grid, size_t ngrid, const T* vals, \
+                                                     size_t nvals, int vals_mem, int device,                 \
+                                                     interpn_hip_interp** handle) {                          \
+    return create_one_dim<T>(method, kRectilinear, (T)0, (T)0, grid, ngrid, vals, nvals, vals_mem, device,   \
+                             handle);                                                                         \
+  }
+DEFINE_CREATE_1D(double, f64)
+DEFINE_CREATE_1D(float, f32)
 
 // Clone an interpolator onto another device of this process.  The grid (`vals`, and the axis image
 // of a rectilinear grid: coordinates + search tables) is copied DEVICE TO DEVICE with

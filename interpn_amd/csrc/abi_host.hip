@@ -163,7 +163,7 @@ static int eval_host_small(interpn_hip_interp* h, const void* const* obs, void* 
   if (good) memcpy(out, host_out, good * elem);
   if (bad != kNoBadIndexHost) {
     if (bad_index) *bad_index = (size_t)bad;
-    return INTERPN_HIP_ERR_UNREPRESENTABLE;
+    return h->desc.unrep_status;
   }
   return INTERPN_HIP_OK;
 }
@@ -209,7 +209,7 @@ int eval_host_impl(interpn_hip_interp* h, const void* const* obs, size_t nobs, v
   if (p.error) return p.error;
   if (p.fail_chunk != ~(size_t)0) {
     if (bad_index) *bad_index = p.fail_index;
-    return INTERPN_HIP_ERR_UNREPRESENTABLE;
+    return h->desc.unrep_status;
   }
   return INTERPN_HIP_OK;
 }
@@ -264,7 +264,7 @@ int interpn_hip_finish(interpn_hip_interp* h, void* stream, uint64_t* first_bad_
   const unsigned long long settled = *(volatile unsigned long long*)h->finish_word;
   if (settled == kNoBadIndexHost) return INTERPN_HIP_OK;  // cannot happen for a monotone MIN word; harmless
   if (first_bad_index) *first_bad_index = (uint64_t)settled;
-  return INTERPN_HIP_ERR_UNREPRESENTABLE;
+  return h->desc.unrep_status;
 }
 
 int interpn_hip_eval_host(interpn_hip_interp* h, const void* const* obs, const size_t* obs_lens, size_t nobs,

@@ -239,6 +239,11 @@ int validate_rectilinear(int method, const T* const* grids, const size_t* grid_l
 // including the flattened cubic arms' `obs.try_into().unwrap()` panic.
 inline int validate_obs(const GridDesc& g, const size_t* obs_lens, size_t nobs, size_t nout) {
   const size_t ndims = (size_t)g.ndims;
+  if (is_one_dim(g.method)) {  // Interp1D::eval(locs, out), one_dim/mod.rs:52-54: one coordinate array
+    if (nobs != 1) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+    if (obs_lens && obs_lens[0] != nout) return INTERPN_HIP_ERR_LENGTH_MISMATCH;
+    return INTERPN_HIP_OK;
+  }
   if (nobs != ndims) {
     if (g.method == kCubic && ndims <= 4) return INTERPN_HIP_ERR_REFERENCE_PANIC;
     return INTERPN_HIP_ERR_DIM_MISMATCH;
@@ -267,6 +272,9 @@ int create_regular(int method, const size_t* dims, size_t ndims, const T* starts
 template <typename T>
 int create_rectilinear(int method, const T* const* grids, const size_t* grid_lens, size_t ngrids, const T* vals,
                        size_t nvals, int vals_mem, int linearize, int device, interpn_hip_interp** handle);
+template <typename T>
+int create_one_dim(int method, int kind, T start, T step, const T* grid, size_t ngrid, const T* vals, size_t nvals,
+                   int vals_mem, int device, interpn_hip_interp** handle);
 
 // abi_launch.hip
 hipError_t launch_any(const GridDesc& g, const void* const* obs, void* out, size_t npts,

@@ -22,6 +22,7 @@ hipError_t launch(const GridDesc& g, const T* const* obs, T* out, size_t npts, u
 
 hipError_t launch_any(const GridDesc& g, const void* const* obs, void* out, size_t npts,
                       unsigned long long* first_bad, hipStream_t stream) {
+  if (is_one_dim(g.method)) return launch_one_dim(g, obs[0], out, npts, first_bad, stream);
   if (g.bricks && npts && g.method == kCubic && !g.cfg.force_generic) {
     if (g.dtype == kF64)
       return launch_cubic_brick<double>(g, reinterpret_cast<const double* const*>(obs), static_cast<double*>(out),

@@ -157,6 +157,14 @@ int maybe_build_records1(interpn_hip_interp* h) {
 
 int maybe_build_bricks(interpn_hip_interp* h) {
   GridDesc& g = h->desc;
+  if (is_one_dim(g.method)) {  // the cell records (k_one_dim.hip) are not optional: the kernel reads nothing else
+    const size_t bytes = (g.od_table_bytes + 15) & ~(size_t)15;
+    HIP_TRY(pool_alloc(h->device, &h->bricks_owned, bytes));
+    HIP_TRY(build_one_dim_table(g, h->bricks_owned, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    g.bricks = h->bricks_owned;
+    return INTERPN_HIP_OK;
+  }
   if (g.method == kCubic && g.ndims >= 2 && g.ndims <= 4) return maybe_build_cubic_tiles(h);
   if (g.method == kLinear && g.ndims == 2) {
     const char* env2 = getenv("INTERPN_HIP_BRICKS");

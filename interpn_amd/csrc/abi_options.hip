@@ -238,6 +238,11 @@ int interpn_hip_kernel_name(const interpn_hip_interp* h, char* buf, size_t bufle
 size_t interpn_hip_table_bytes(const interpn_hip_interp* h, int* step_i, int* step_j) {
   if (!h || !h->desc.bricks) return 0;
   const GridDesc& g = h->desc;
+  if (is_one_dim(g.method)) {
+    if (step_i) *step_i = 0;
+    if (step_j) *step_j = 0;
+    return g.od_table_bytes;
+  }
   if (step_i) *step_i = g.brick_step[0];
   if (step_j) *step_j = g.brick_step[1];
   size_t bytes = 0;

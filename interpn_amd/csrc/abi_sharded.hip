@@ -93,7 +93,7 @@ int interpn_hip_eval_host_sharded(interpn_hip_interp* const* handles, size_t nha
   for (auto& w : workers) w.join();
   // Ranges ascend with r, so the first failing range holds the globally first failing point.
   for (size_t r = 0; r < nhandles; ++r) {
-    if (status[r] == INTERPN_HIP_ERR_UNREPRESENTABLE) {
+    if (status[r] == handles[r]->desc.unrep_status) {
       if (first_bad_index) *first_bad_index = (uint64_t)(lo[r] + bad[r]);
       return status[r];
     }
@@ -133,7 +133,7 @@ int interpn_hip_eval_device_sharded(interpn_hip_interp* const* handles, size_t n
     if (launched[r]) {
       uint64_t bad = 0;
       const int st = interpn_hip_finish(handles[r], streams ? streams[r] : nullptr, &bad);
-      if (st == INTERPN_HIP_ERR_UNREPRESENTABLE) {
+      if (st == handles[r]->desc.unrep_status) {
         if (offset + bad < best) best = offset + bad;
       } else if (st != INTERPN_HIP_OK && first_error == INTERPN_HIP_OK) {
         first_error = st;
@@ -144,7 +144,7 @@ int interpn_hip_eval_device_sharded(interpn_hip_interp* const* handles, size_t n
   if (first_error != INTERPN_HIP_OK) return first_error;
   if (best != ~(uint64_t)0) {
     if (first_bad_index) *first_bad_index = best;
-    return INTERPN_HIP_ERR_UNREPRESENTABLE;
+    return handles[0]->desc.unrep_status;
   }
   return INTERPN_HIP_OK;
 }

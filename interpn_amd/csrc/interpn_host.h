@@ -10,6 +10,10 @@
 namespace interpn {
 
 enum Method : int { kLinear = 0, kCubic = 1, kNearest = 2 };
+// interpn::one_dim (src/one_dim/*.rs): the five one-dimensional interpolators, method codes of their own
+// (include/interpn_hip.h INTERPN_HIP_*_1D), evaluated by k_one_dim.hip only.
+enum OneDimMethod : int { kLinear1D = 16, kLinearHoldLast1D = 17, kLeft1D = 18, kRight1D = 19, kNearest1D = 20 };
+inline bool is_one_dim(int method) { return method >= kLinear1D && method <= kNearest1D; }
 enum Kind : int { kRegular = 0, kRectilinear = 1 };
 enum DType : int { kF64 = 0, kF32 = 1 };
 
@@ -161,6 +165,18 @@ struct GridDesc {
   // (multilinear/regular.rs:160-166: starts + steps*(dims-1), min/max; rectilinear.rs:121-123).
   double bound_lo[8] = {0};
   double bound_hi[8] = {0};
+  // Status of a point the handle cannot evaluate: INTERPN_HIP_ERR_UNREPRESENTABLE ("Unrepresentable coordinate value") for
+  // the multidimensional methods, INTERPN_HIP_ERR_UNREPRESENTABLE_NUMBER ("Unrepresentable number") for one_dim.
+  int unrep_status = 7;
+  // one_dim (k_one_dim.hip).  Regular: od_start / od_step / od_stop as the element type holds them (one_dim/mod.rs:86-95),
+  // od_fast = 1 where the step admits the divide-free cell index.  Rectilinear: od_M buckets over [g[0], g[n-1]] (0: the
+  // std probe sequence).  `bricks` holds the table: n - 1 cell records, then (rectilinear) the coordinates at od_g_off and
+  // the bucket table at od_tab_off; od_table_bytes in all.
+  double od_start = 0, od_step = 0, od_stop = 0, od_rstep = 0;
+  int od_fast = 0;
+  int od_M = 0;
+  double od_g0 = 0, od_scale = 0;
+  size_t od_g_off = 0, od_tab_off = 0, od_table_bytes = 0;
   LaunchConfig cfg;
   mutable KernelTag tag;
   mutable int last_binned = 0;  // the most recent device-pointer evaluation sorted its points first (binned evaluation)
@@ -283,6 +299,12 @@ size_t records1_bytes(const GridDesc& g, int M);
 hipError_t build_records1(const GridDesc& g, int M, double scale, void* recs, unsigned* maxpop_dev, hipStream_t stream);
 template <typename T>
 hipError_t launch_linear1_records(const GridDesc& g, const T* const* obs, T* out, size_t npts, hipStream_t stream);
+
+// one_dim (k_one_dim.hip): the table of a handle (layout above), built on the device from `vals` and the grid; the launch.
+size_t one_dim_record_bytes(const GridDesc& g);
+hipError_t build_one_dim_table(const GridDesc& g, void* table, hipStream_t stream);
+hipError_t launch_one_dim(const GridDesc& g, const void* obs, void* out, size_t npts, unsigned long long* first_bad,
+                          hipStream_t stream);
 
 // Bricked 2-D multilinear path (k_linear2_brick.hip): 2 x KW2 bricks, steps (1, KW2-1).
 void brick2_geometry(const GridDesc& g, unsigned nb[2], size_t* bytes);

@@ -91,6 +91,45 @@ class Interpolator:
         _lib.raise_for_status(st)
         return cls(h.value, dtype, ng, keep if mem == _lib.MEM_DEVICE else None)
 
+    @classmethod
+    def grid1d_regular(cls, method: str, start, step, vals, device: int = -1, dtype=None, fma=None) -> "Interpolator":
+        """interpn::one_dim on RegularGrid1D::new(start, step, vals) (`interpn_hip_create_grid1d_regular_*`);
+        `method` is one of "Linear1D", "LinearHoldLast1D", "Left1D", "Right1D", "Nearest1D"."""
+        if dtype is None:
+            dtype = vals.dtype if isinstance(vals, np.ndarray) else np.float64
+        dtype = np.dtype(dtype)
+        sfx = "f64" if dtype == np.float64 else "f32"
+        lib = _lib.load()
+        vptr, nvals, mem, keep = cls._vals_arg(vals, dtype)
+        h = c_void_p()
+        st = getattr(lib, f"interpn_hip_create_grid1d_regular_{sfx}")(
+            cls._method_arg_1d(method, fma), float(start), float(step), vptr, nvals, mem, int(device), ctypes.byref(h))
+        _lib.raise_for_status(st)
+        return cls(h.value, dtype, 1, keep if mem == _lib.MEM_DEVICE else None)
+
+    @classmethod
+    def grid1d_rectilinear(cls, method: str, grid, vals, device: int = -1, dtype=None, fma=None) -> "Interpolator":
+        """interpn::one_dim on RectilinearGrid1D::new(grid, vals) (`interpn_hip_create_grid1d_rectilinear_*`)."""
+        dtype = np.dtype(dtype or grid.dtype)
+        sfx = "f64" if dtype == np.float64 else "f32"
+        ct = c_double if dtype == np.float64 else c_float
+        lib = _lib.load()
+        g = _check_arr("grid", grid, dtype)
+        vptr, nvals, mem, keep = cls._vals_arg(vals, dtype)
+        h = c_void_p()
+        st = getattr(lib, f"interpn_hip_create_grid1d_rectilinear_{sfx}")(
+            cls._method_arg_1d(method, fma), g.ctypes.data_as(POINTER(ct)), g.size, vptr, nvals, mem, int(device),
+            ctypes.byref(h))
+        _lib.raise_for_status(st)
+        return cls(h.value, dtype, 1, keep if mem == _lib.MEM_DEVICE else None)
+
+    @staticmethod
+    def _method_arg_1d(method: str, fma) -> int:
+        m = _lib.METHODS_1D[method]
+        if fma is None:
+            return m
+        return m | (_lib.FLAVOUR_FMA if fma else _lib.FLAVOUR_NO_FMA)
+
     def replicate(self, device: int = -1) -> "Interpolator":
         """Clone onto another GPU of this process, grid copied device to device
         (`interpn_hip_replicate`); the clone owns its copy."""
@@ -280,18 +319,20 @@ class Interpolator:
             except ImportError:
                 raws = [0]
         first_bad = None
+        first_bad_status = _lib.ERR_UNREPRESENTABLE
         status = _lib.OK
         for raw in raws:
             bad = c_uint64(0)
             st = lib.interpn_hip_finish(self._h, c_void_p(int(raw)), ctypes.byref(bad))
             self._pending_streams.pop(raw, None)
-            if st == _lib.ERR_UNREPRESENTABLE:
+            if st in _lib.UNREPRESENTABLE:
+                first_bad_status = st
                 first_bad = bad.value if first_bad is None else min(first_bad, bad.value)
             elif st != _lib.OK and status == _lib.OK:
                 status = st
         _lib.raise_for_status(status)
         if first_bad is not None:
-            err = AssertionError(_lib.strerror(_lib.ERR_UNREPRESENTABLE))
+            err = AssertionError(_lib.strerror(first_bad_status))
             err.first_bad_index = first_bad
             raise err
 
@@ -328,7 +369,7 @@ def eval_host_sharded(interps, obs, out: np.ndarray) -> np.ndarray:
     bad = c_uint64(0)
     st = lib.interpn_hip_eval_host_sharded(hs, len(interps), vp, olen, nobs, out.ctypes.data_as(c_void_p), out.size,
                                            ctypes.byref(bad))
-    if st == _lib.ERR_UNREPRESENTABLE:
+    if st in _lib.UNREPRESENTABLE:
         err = AssertionError(_lib.strerror(st))
         err.first_bad_index = bad.value
         raise err
@@ -380,7 +421,7 @@ def eval_device_sharded(interps, obs_shards, out_shards=None):
         streams[r] = torch.cuda.current_stream(shard[0].device).cuda_stream
     bad = c_uint64(0)
     st = lib.interpn_hip_eval_device_sharded(hs, n, obs_pp, nd, out_p, npts, streams, ctypes.byref(bad))
-    if st == _lib.ERR_UNREPRESENTABLE:
+    if st in _lib.UNREPRESENTABLE:
         err = AssertionError(_lib.strerror(st))
         err.first_bad_index = bad.value
         raise err
