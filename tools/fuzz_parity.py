@@ -2,6 +2,7 @@
 """Differential fuzz: random (method, kind, N, axis sizes, dtype, linearize, layout knobs, batch
 size, special coordinates) through the C ABI against the CPU oracle, bit for bit.
     python tools/fuzz_parity.py [seconds=120] [seed=0]
+    python tools/fuzz_parity.py one_dim [seconds=120] [seed=0]     interpn::one_dim against tests/one_dim_restatement.py
 Prints one line per failure and a summary; exit code 1 if anything differed."""
 import os, sys, time
 import numpy as np
@@ -250,7 +251,147 @@ def run(budget: float, seed: int, max_cases: int = 0):
     return n_cases, n_fail
 
 
+def _one_dim_grid(rng, kind, dtype, n):
+    """A grid from the step / axis families of tests/test_one_dim_gpu.py: (args, lo, hi) with [lo, hi] its finite extent."""
+    T = np.dtype(dtype).type
+    fi = np.finfo(dtype)
+    vals = rng.normal(size=n).astype(dtype)
+    if kind == "regular":
+        lo_s, hi_s = (2.0**-128, 2.0**128) if dtype == np.float64 else (2.0**-16, 2.0**16)  # StepCellRange<T>
+        fam = int(rng.integers(0, 7))
+        if fam == 0: step = 0.0731
+        elif fam == 1: step = 1.0 / 3.0
+        elif fam == 2: step = 2.5 / (n - 1)
+        elif fam == 3: step = 2.0 ** float(rng.integers(-12, 8))
+        elif fam == 4: step = float(rng.choice([lo_s, hi_s])) * float(rng.choice([1.0, 1.0 + 4 * fi.eps, 1.0 - 4 * fi.eps]))
+        elif fam == 5: step = float(rng.uniform(1e-4, 10.0))
+        else: step = float(rng.choice([0.0, -0.125, np.nan]))  # degenerate: the division path, every point may fail
+        start = float(rng.choice([0.0, -1.25, 1e6, -3e3])) if fam != 4 else 0.0
+        start, step = T(start), T(step)
+        with np.errstate(all="ignore"):
+            stop = T(start + step * T(n - 1))
+        return dict(start=start, step=step, vals=vals), float(start), float(stop)
+    fam = int(rng.integers(0, 6))
+    if fam == 0:
+        g = np.cumsum(rng.uniform(0.1, 1.0, size=n)) - 0.3 * n
+    elif fam == 1:  # one cluster of knots 1 ulp apart inside a wide axis
+        m = min(n - 2, 4000)
+        c = np.empty(m, dtype=dtype)
+        v = T(rng.uniform(1.0, 2.0))
+        for j in range(m):
+            c[j] = v
+            v = np.nextafter(v, T(np.inf))
+        rest = rng.uniform(3.0, 1e4, size=n - m - 1)
+        g = np.concatenate([[-50.0], c.astype(np.float64), rest])
+    elif fam == 2:
+        g = rng.uniform(-1.0, 1.0, size=n) * float(rng.choice([1e-30, 1.0, 1e30]))
+    elif fam == 3:  # huge span: overflows in f64, M / span subnormal in f32
+        g = np.concatenate([[-0.9 * float(fi.max)], rng.uniform(-10.0, 10.0, size=n - 2), [0.9 * float(fi.max)]])
+    elif fam == 4:
+        g = np.concatenate([[-np.inf], rng.uniform(-10.0, 10.0, size=n - 2), [np.inf]]) if n > 2 else np.array([-1.0, np.inf])
+    else:
+        g = rng.normal(size=n)  # unsorted: the std probe sequence
+    with np.errstate(all="ignore"):
+        g = g.astype(dtype)
+    if fam != 5:
+        g = np.unique(g)
+        vals = vals[:len(g)]
+    if len(g) < 2:
+        g, vals = np.array([0.0, 1.0], dtype=dtype), vals[:2] if len(vals) >= 2 else np.zeros(2, dtype=dtype)
+    fin = g[np.isfinite(g)]
+    return dict(grid=g, vals=vals), float(fin.min()), float(fin.max())
+
+
+def run_one_dim(budget: float, seed: int, max_cases: int = 0):
+    """interpn::one_dim against tests/one_dim_restatement.py, bit for bit.  Returns (cases, failures)."""
+    import torch
+
+    from interpn_amd import Interpolator
+    from tests import one_dim_restatement as R
+
+    rng = np.random.default_rng(seed)
+    t_end = time.time() + budget
+    n_cases = n_fail = 0
+    while time.time() < t_end and (max_cases == 0 or n_cases < max_cases):
+        method = str(rng.choice(R.METHODS))
+        kind = str(rng.choice(["regular", "rectilinear"]))
+        dtype = np.float64 if rng.random() < 0.5 else np.float32
+        fma = bool(rng.integers(0, 2))
+        n = int(rng.choice([2, 3, int(rng.integers(2, 200)), int(rng.integers(2, 70_001))]))
+        args, lo, hi = _one_dim_grid(rng, kind, dtype, n)
+        npts = int(rng.choice([1, 2, 3, int(rng.integers(1, 600)), int(rng.integers(1, 9000)), int(rng.integers(1, 60_000))]))
+        span = hi - lo if np.isfinite(hi - lo) and hi > lo else 1.0
+        with np.errstate(all="ignore"):
+            x = np.concatenate([rng.uniform(lo - 0.3 * span, lo + 1.3 * span, npts)[: max(1, npts - npts // 4)],
+                                (lo + span * rng.integers(0, 64, npts // 4) / 64.0)])[:npts].astype(dtype)
+            near = rng.random(npts) < 0.2  # a fifth of the points moved a few ulps
+            for j in range(int(rng.integers(1, 4))):
+                x[near] = np.nextafter(x[near], dtype(rng.choice([-np.inf, np.inf])))
+        inject = rng.random() < 0.3
+        if inject:
+            for _ in range(int(rng.integers(1, 4))):
+                x[int(rng.integers(0, npts))] = rng.choice([np.nan, np.inf, -np.inf])
+        if not inject:
+            x[~np.isfinite(x)] = dtype(lo)
+        want, bad = R.eval(method, kind, dtype, fma, x, **args)
+        opts = {"ppl": int(rng.choice([0, 0, 1])), "axis_lds_kb": int(rng.choice([-1, -1, 0, 1, 60]))}
+        device_path = bool(rng.random() < 0.5)
+        err = first_bad = None
+        ok = True
+        try:
+            if kind == "regular":
+                it = Interpolator.grid1d_regular(method, args["start"], args["step"], args["vals"], device=0, dtype=dtype, fma=fma)
+            else:
+                it = Interpolator.grid1d_rectilinear(method, args["grid"], args["vals"], device=0, dtype=dtype, fma=fma)
+            for k, v in opts.items():
+                it.set_option(k, v)
+            if device_path:
+                tt = torch.float64 if dtype == np.float64 else torch.float32
+                o1, o2 = int(rng.integers(0, 4)), int(rng.integers(2, 6))
+                ob = torch.zeros(npts + o1, dtype=tt, device="cuda:0")
+                ob[o1:] = torch.from_numpy(x)
+                full = torch.full((npts + o2 + 2,), -777.0, dtype=tt, device="cuda:0")
+                it.eval_tensors([ob[o1:]], full[o2:o2 + npts])
+                try:
+                    it.finish()
+                except AssertionError as e:
+                    err, first_bad = str(e), getattr(e, "first_bad_index", None)
+                h = full.cpu().numpy()
+                got = h[o2:o2 + npts]
+                ok = bool(np.all(h[:o2] == -777.0) and np.all(h[o2 + npts:] == -777.0))  # guards
+            else:
+                got = np.full(npts, -777.0, dtype=dtype)
+                try:
+                    it.eval_host([x], got)
+                except AssertionError as e:
+                    err = str(e)
+                if bad is not None:
+                    ok = bool(np.all(got[bad:] == dtype(-777.0)))  # host: untouched from the first bad point on
+                    first_bad = bad
+            name = it.kernel_name()
+            it.close()
+            k = npts if bad is None else bad
+            same = ((got[:k] == want[:k]) & (np.signbit(got[:k]) == np.signbit(want[:k]))) | (np.isnan(got[:k]) & np.isnan(want[:k]))
+            ok = ok and bool(same.all()) and (err == "Unrepresentable number") == (bad is not None) and (bad is None or first_bad == bad)
+            ok = ok and "k_one_dim<" in name and (opts["ppl"] != 1 or name.endswith(", 1>")) and (opts["axis_lds_kb"] != 0 or ", false, " in name[-12:])
+        except Exception as e:  # noqa: BLE001
+            ok, err = False, "EXC " + repr(e)
+        n_cases += 1
+        if not ok:
+            n_fail += 1
+            desc = {k: (v if np.ndim(v) == 0 else f"<{len(v)}>") for k, v in args.items()}
+            print(f"FAIL one_dim method={method} kind={kind} dtype={np.dtype(dtype).name} fma={fma} n={n} npts={npts} grid={desc} "
+                  f"opts={opts} device_path={device_path} inject={inject} bad={bad} first_bad={first_bad} err={err!r}", flush=True)
+    return n_cases, n_fail
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "one_dim":
+        budget = float(sys.argv[2]) if len(sys.argv) > 2 else 120.0
+        seed = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+        n_cases, n_fail = run_one_dim(budget, seed)
+        print(f"fuzz one_dim: {n_cases} cases, {n_fail} failures, seed {seed}, {budget:.0f} s")
+        sys.exit(1 if n_fail else 0)
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     n_cases, n_fail = run(budget, seed)
