@@ -431,6 +431,101 @@ int interpn_hip_check_bounds_device(interpn_hip_interp* h, const void* const* ob
 INTERPN_HIP_DECLARE_BOUNDS(double, f64)
 INTERPN_HIP_DECLARE_BOUNDS(float, f32)
 
+/* ------------------------------------------------------------------------------------------
+ * Field sets — K value grids ("fields") that live on ONE grid, evaluated at the same points: equation-of-state
+ * and opacity tables, vector fields, colour channels, scipy's RegularGridInterpolator with trailing value
+ * dimensions.  K single handles read the same coordinates K times, search the same cell K times and each visit
+ * table lines of their own; a set does the first two once and, on its fused path, fetches lines that hold
+ * several fields of one cell.
+ *
+ * Input     `vals` is field-major: field f is the C-ordered grid at vals + f * field_stride (elements), `nvals`
+ *           counts the whole buffer.  `method` as for interpn_hip_create_* (flavour bits included).
+ * Checks    all before any device work: nfields == 0, field_stride < prod(dims), nvals < (nfields - 1) *
+ *           field_stride + prod(dims): INTERPN_HIP_ERR_INVALID_ARGUMENT; then the single-field creator's checks
+ *           on one field, with its statuses, order and strings (a field's length is prod(dims) by construction,
+ *           so the reference's "Dimension mismatch" on vals.len() cannot occur; the one on starts / steps can).
+ * Contract  row f of a result is bit-identical to what the single handle of field f returns — on both paths,
+ *           in both fma flavours — and therefore to the reference.  A point the reference cannot evaluate fails
+ *           for every field at once: the host form returns INTERPN_HIP_ERR_UNREPRESENTABLE with out[f][0..i)
+ *           written for every f and out[f][i..] untouched; the device form reports i through
+ *           interpn_hip_fields_finish.
+ * Paths     FUSED (multilinear, N = 2 or 3, regular and rectilinear, f64 and f32, any K): one kernel,
+ *           interpn::k_linear_fields, on a table built on the device at creation — one 128-byte line = the 2^N
+ *           corners of one cell for P = 128 / (2^N * elem_size) consecutive fields (dimension 0's pair innermost),
+ *           the ceil(K / P) lines of a cell contiguous, cells in C order, missing fields zero.  Asynchronous,
+ *           allocates nothing, can be captured into a graph.
+ *           PER_FIELD (every method, kind, N and type the single handles support, and every set without the
+ *           table): K evaluations through K ordinary handles on the caller's stream, each with all the tuned paths
+ *           and options of interpn_hip_eval_device_ex (sorting, sweep, in place under capture).
+ * Memory    a set owns one device copy of `vals` (or borrows the caller's device buffer, which must outlive it),
+ *           K ordinary handles on slices of it (INTERPN_HIP_MEM_DEVICE; each keeps its own copy of a rectilinear
+ *           grid's axes, a few KiB), and the fused table: prod(n_d - 1) * ceil(K / P) * 128 bytes
+ *           (interpn_hip_fields_layout), built only while it fits a quarter of the free device memory — the rule of
+ *           the single handles' tables; otherwise the set is per-field only, which is not an error ("fused_table_bytes"
+ *           = 0).  The K handles of a set that has the fused table build their own re-laid tables (up to 16 x a
+ *           field each, see the memory note at the top) only when the per-field path is first used outside graph
+ *           capture and without INTERPN_HIP_EVAL_NO_ALLOC — a synchronous step of that one call, which reads
+ *           INTERPN_HIP_BRICKS then; until then per-field evaluations read the C-ordered fields (same bits).
+ * Options   interpn_hip_fields_set_option / _get_option: "fused" = -1 automatic, 0 never, 1 wherever the set has the
+ *           table.  Automatic (from measurements): per field where the lines of the table would be
+ *           less than 3/4 full (4 K < 3 ceil(K / P) P, e.g. K = 2 in f32), and for 3-D f64 sets whose fields are L2-sized
+ *           on batches that the single handles evaluate with the sweep kernel outside graph capture; fused otherwise;
+ *           read-only "fused_table_bytes", "nfields", "last_path"; every other name is
+ *           passed to the K handles (set: all of them, get: the first), e.g. "blocks_per_cu" (the fused kernel's
+ *           persistent grid is sized with it too), "fma", "host_chunk", "sweep".  Latched at creation:
+ *           INTERPN_HIP_FIELDS_FUSED=-1|0|1 (0 also skips building the table) and, for tests,
+ *           INTERPN_HIP_FIELDS_TABLE_BUDGET=bytes (the table is built only up to this size).
+ * Not here  replicate / sharded forms; check_bounds on a set (the bounds are those of the grid: use
+ *           interpn_hip_check_bounds_regular_* / _rectilinear_*); interpn::one_dim; a mirror in interpn_hip.hpp
+ *           (the reference crate has no such API).
+ * Threads   as for single handles; host evaluations of one set are serialised, and they share the sticky status
+ *           words with the device form: finish device evaluations before evaluating on host arrays.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct interpn_hip_fields interpn_hip_fields;
+
+#define INTERPN_HIP_DECLARE_FIELDS(T, SUFFIX)                                                                     \
+  int interpn_hip_create_fields_regular_##SUFFIX(int method, const size_t* dims, size_t ndims, const T* starts,  \
+                                                 size_t nstarts, const T* steps, size_t nsteps, const T* vals,   \
+                                                 size_t nvals, size_t nfields, size_t field_stride,              \
+                                                 int vals_mem, int linearize_extrapolation, int device,          \
+                                                 interpn_hip_fields** fields);                                   \
+  int interpn_hip_create_fields_rectilinear_##SUFFIX(int method, const T* const* grids,                          \
+                                                     const size_t* grid_lens, size_t ngrids, const T* vals,      \
+                                                     size_t nvals, size_t nfields, size_t field_stride,          \
+                                                     int vals_mem, int linearize_extrapolation, int device,      \
+                                                     interpn_hip_fields** fields);
+
+INTERPN_HIP_DECLARE_FIELDS(double, f64)
+INTERPN_HIP_DECLARE_FIELDS(float, f32)
+
+/* Evaluate every field on device arrays (asynchronous on `stream`): `obs` as for interpn_hip_eval_device, `out` a
+ * device pointer, out[f * out_stride + i] = field f at point i (out_stride >= npoints, in elements).  `flags`:
+ * INTERPN_HIP_EVAL_NO_ALLOC (the fused path never allocates).  *path_taken (may be NULL): which path ran. */
+enum { INTERPN_HIP_FIELDS_PATH_FUSED = 0, INTERPN_HIP_FIELDS_PATH_PER_FIELD = 1 };
+int interpn_hip_fields_eval_device(interpn_hip_fields* fields, const void* const* obs, size_t nobs, void* out,
+                                   size_t out_stride, size_t npoints, void* stream, unsigned flags, int* path_taken);
+/* The same on host arrays (synchronous): chunks of at most 2 Mi points (option "host_chunk"), each chunk's coordinates
+ * cross PCIe once for all fields.  nobs == ndims, obs_lens[d] == nout, out_stride >= nout. */
+int interpn_hip_fields_eval_host(interpn_hip_fields* fields, const void* const* obs, const size_t* obs_lens, size_t nobs,
+                                 void* out, size_t out_stride, size_t nout);
+/* interpn_hip_finish for a set: waits for `stream`, reports and clears the sticky status of its device evaluations. */
+int interpn_hip_fields_finish(interpn_hip_fields* fields, void* stream, uint64_t* first_bad_index);
+/* Waits for the work enqueued through the set (as interpn_hip_destroy does for a handle), then releases everything. */
+void interpn_hip_fields_destroy(interpn_hip_fields* fields);
+size_t interpn_hip_fields_count(const interpn_hip_fields* fields);
+int interpn_hip_fields_ndims(const interpn_hip_fields* fields);
+int interpn_hip_fields_elem_size(const interpn_hip_fields* fields);
+int interpn_hip_fields_device(const interpn_hip_fields* fields);
+/* Kernel of the most recent evaluation: "interpn::k_linear_fields<double, 3, false, true>" (type, N, rectilinear, fma)
+ * after a fused one, the first field's kernel after a per-field one. */
+int interpn_hip_fields_kernel_name(const interpn_hip_fields* fields, char* buf, size_t buflen);
+int interpn_hip_fields_set_option(interpn_hip_fields* fields, const char* name, long long value);
+int interpn_hip_fields_get_option(const interpn_hip_fields* fields, const char* name, long long* value);
+/* The fused table of `nfields` fields of `elem_size` (4, 8) bytes on a grid of `dims` (ndims = 2, 3; every axis >= 2):
+ * P, ceil(nfields / P) and the table's size.  Needs no device.  INTERPN_HIP_ERR_INVALID_ARGUMENT for anything else. */
+int interpn_hip_fields_layout(size_t elem_size, size_t ndims, const size_t* dims, size_t nfields, int* fields_per_line,
+                              size_t* lines_per_point, size_t* table_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib, one_dim, raw
 from .classes import (MulticubicRectilinear, MulticubicRegular, MultilinearRectilinear, MultilinearRegular,
                       NearestRectilinear, NearestRegular)
+from .fields import Fields, fields_layout, interpn_fields
 from .handle import Interpolator, eval_device_sharded, eval_host_sharded
 
 __version__ = "0.1.0"
@@ -38,6 +39,9 @@ __all__ = [
     "__version__",
     "raw",
     "interpn",
+    "interpn_fields",
+    "Fields",
+    "fields_layout",
     "Interpolator",
     "MultilinearRegular",
     "MultilinearRectilinear",

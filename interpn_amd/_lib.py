@@ -32,6 +32,7 @@ METHODS_1D = {"Linear1D": 16, "LinearHoldLast1D": 17, "Left1D": 18, "Right1D": 1
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAVOUR_FMA, FLAVOUR_NO_FMA = 0x100, 0x200  # OR-ed into `method` of interpn_hip_create_*
 PATH_IN_PLACE, PATH_BINNED, PATH_SWEEP = 0, 1, 2
+FIELDS_PATH_FUSED, FIELDS_PATH_PER_FIELD = 0, 1  # interpn_hip_fields_eval_device
 EVAL_NO_ALLOC = 1
 WHY = {0: "", 1: "batch below the break-even size or option binned = 0", 2: "stream under graph capture",
        3: "no reserved scratch block free and allocation not allowed", 4: "scratch allocation failed",
@@ -119,6 +120,11 @@ def load() -> ctypes.CDLL:
             c_int, ct, ct, c_void_p, c_size_t, c_int, c_int, POINTER(c_void_p)]
         getattr(lib, f"interpn_hip_create_grid1d_rectilinear_{sfx}").argtypes = [
             c_int, p, c_size_t, c_void_p, c_size_t, c_int, c_int, POINTER(c_void_p)]
+        getattr(lib, f"interpn_hip_create_fields_regular_{sfx}").argtypes = [
+            c_int, sz, c_size_t, p, c_size_t, p, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_int,
+            POINTER(c_void_p)]
+        getattr(lib, f"interpn_hip_create_fields_rectilinear_{sfx}").argtypes = [
+            c_int, pp, sz, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_int, c_int, POINTER(c_void_p)]
         getattr(lib, f"interpn_hip_check_bounds_regular_{sfx}").argtypes = [
             sz, c_size_t, p, c_size_t, p, c_size_t, pp, sz, c_size_t, ct, POINTER(c_uint8), c_size_t]
         getattr(lib, f"interpn_hip_check_bounds_rectilinear_{sfx}").argtypes = [
@@ -148,6 +154,23 @@ def load() -> ctypes.CDLL:
     lib.interpn_hip_table_bytes.restype = c_size_t
     lib.interpn_hip_destroy.argtypes = [c_void_p]
     lib.interpn_hip_destroy.restype = None
+    lib.interpn_hip_fields_eval_device.argtypes = [c_void_p, POINTER(c_void_p), c_size_t, c_void_p, c_size_t, c_size_t, c_void_p,
+                                                   ctypes.c_uint, POINTER(c_int)]
+    lib.interpn_hip_fields_eval_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_size_t,
+                                                 c_size_t]
+    lib.interpn_hip_fields_finish.argtypes = [c_void_p, c_void_p, POINTER(c_uint64)]
+    lib.interpn_hip_fields_destroy.argtypes = [c_void_p]
+    lib.interpn_hip_fields_destroy.restype = None
+    lib.interpn_hip_fields_count.argtypes = [c_void_p]
+    lib.interpn_hip_fields_count.restype = c_size_t
+    lib.interpn_hip_fields_ndims.argtypes = [c_void_p]
+    lib.interpn_hip_fields_elem_size.argtypes = [c_void_p]
+    lib.interpn_hip_fields_device.argtypes = [c_void_p]
+    lib.interpn_hip_fields_kernel_name.argtypes = [c_void_p, ctypes.c_char_p, c_size_t]
+    lib.interpn_hip_fields_set_option.argtypes = [c_void_p, c_char_p, ctypes.c_longlong]
+    lib.interpn_hip_fields_get_option.argtypes = [c_void_p, c_char_p, POINTER(ctypes.c_longlong)]
+    lib.interpn_hip_fields_layout.argtypes = [c_size_t, c_size_t, POINTER(c_size_t), c_size_t, POINTER(c_int), POINTER(c_size_t),
+                                              POINTER(c_size_t)]
     _lib = lib
     return lib
 

@@ -8,6 +8,8 @@ using namespace interpn_abi;
 
 namespace interpn_abi {
 
+thread_local bool t_defer_tables = false;
+
 int finish_create(interpn_hip_interp* h, const void* vals, size_t nvals, size_t elem, int vals_mem) {
   GridDesc& g = h->desc;
   {
@@ -30,6 +32,7 @@ int finish_create(interpn_hip_interp* h, const void* vals, size_t nvals, size_t 
   HIP_TRY(pool_alloc(h->device, (void**)&h->first_bad, sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(h->first_bad, 0xFF, sizeof(unsigned long long), nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
+  if (t_defer_tables) return INTERPN_HIP_OK;
   int st = maybe_build_bricks(h);
   if (st) return st;
   return INTERPN_HIP_OK;

@@ -264,6 +264,9 @@ bool option_access(LaunchConfig& c, const char* name, long long* value, bool set
 void latch_env(LaunchConfig& c);
 
 // abi_create.hip
+// Set by the field-set creators (abi_fields.hip) around the creation of their per-field handles: finish_create then
+// leaves the re-laid table out, and maybe_build_bricks is called when the per-field path is first used.
+extern thread_local bool t_defer_tables;
 int finish_create(interpn_hip_interp* h, const void* vals, size_t nvals, size_t elem, int vals_mem);
 template <typename T>
 int create_regular(int method, const size_t* dims, size_t ndims, const T* starts, size_t nstarts, const T* steps,

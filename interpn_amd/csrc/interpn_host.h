@@ -294,6 +294,21 @@ template <typename T>
 hipError_t launch_linear_brick(const GridDesc& g, const T* const* obs, T* out, size_t npts,
                                unsigned long long* first_bad, hipStream_t stream);
 
+// Field sets (k_linear_fields.hip, linear_fields.h): K value grids on one grid, evaluated in one pass over the points
+// out of a table whose 128-byte lines hold one cell's corners for `fields_per_line` consecutive fields.
+struct FieldsGeometry {
+  int fields_per_line = 0;   // P = 128 / (2^N * element size)
+  size_t lines_per_point = 0;  // ceil(K / P): the lines of a cell, contiguous
+  size_t cells = 0;          // prod(n_d - 1)
+  size_t table_bytes = 0;    // cells * lines_per_point * 128; 0 with `false`: the size does not fit size_t
+};
+// false: no fused form for this element size / dimension count (N = 2, 3 only), an axis shorter than 2, or no fields
+bool fields_geometry(size_t elem_size, int ndims, const size_t* dims, size_t nfields, FieldsGeometry* out);
+// `g`: the description of any one field's handle (grid, axes, flavour, options); `vals`: the field-major device buffer
+hipError_t build_fields_table(const GridDesc& g, const void* vals, size_t field_stride, int nfields, void* table, hipStream_t stream);
+hipError_t launch_linear_fields(const GridDesc& g, const void* table, int nfields, const void* const* obs, void* out,
+                                size_t out_stride, size_t npts, unsigned long long* first_bad, hipStream_t stream);
+
 // 1-D multilinear-rectilinear from per-bucket records (k_linear1_records.hip).
 size_t records1_bytes(const GridDesc& g, int M);
 hipError_t build_records1(const GridDesc& g, int M, double scale, void* recs, unsigned* maxpop_dev, hipStream_t stream);
