@@ -526,6 +526,68 @@ int interpn_hip_fields_get_option(const interpn_hip_fields* fields, const char* 
 int interpn_hip_fields_layout(size_t elem_size, size_t ndims, const size_t* dims, size_t nfields, int* fields_per_line,
                               size_t* lines_per_point, size_t* table_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * Lattice evaluation — the points are the tensor product of N coordinate vectors, one per axis: re-gridding,
+ * RegularGridInterpolator on a meshgrid, resampling a volume, refining a table.  The caller passes the N vectors
+ * (sum of their lengths coordinates) instead of N arrays of prod(lengths) coordinates; out[i_0, .., i_{N-1}] (C order,
+ * last axis contiguous) is the interpolant at (axes[0][i_0], .., axes[N-1][i_{N-1}]).  The vectors need not be sorted.
+ *
+ * Contract  every result is bit-identical to what interpn_hip_eval_device gives for the expanded point, in both fma
+ *           flavours, and therefore to the reference.
+ * Paths     FUSED (multilinear and multicubic, N = 2 or 3, regular and rectilinear, f64 and f32, grids that 32 bits
+ *           index): interpn::k_lattice_axes turns every axis coordinate into a record (cell, normalized coordinate,
+ *           cubic class, rectilinear spacing ratios) with the device functions of the per-point kernels;
+ *           interpn::k_lattice_rows then reduces dims 0..N-2 once per output row and grid column of the last axis into
+ *           an LDS line and evaluates every output of the row as one node of the last dimension.  Per point it moves
+ *           sizeof(T) bytes instead of (N + 1) sizeof(T).  Condition: four lines of n_{N-1} elements fit the LDS budget
+ *           of rectilinear axis images (20 KiB; option "axis_lds_kb").
+ *           EXPANDED (everything else: nearest, N = 1, N >= 4, longer last axes): interpn::k_lattice_expand writes the
+ *           coordinates of a slice of the lattice (64 MiB at most) into scratch, and the slice goes through
+ *           interpn_hip_eval_device_ex with all its paths and options.
+ * Options   "lattice" = -1 automatic, 0 never fused, 1 fused wherever covered.  Automatic takes the fused path when,
+ *           in addition, the lattice has a row for every wave of the device (prod(m_0..m_{N-2}) >= 4 x CUs) and the last
+ *           grid axis is not much longer than the last lattice axis (n_{N-1} <= 4 max(m_{N-1}, 64)): DESIGN.md.
+ *           Read-only "last_lattice_path" (INTERPN_HIP_LATTICE_PATH_*; -1 before any).  interpn_hip_kernel_name reports
+ *           "interpn::k_lattice_rows<T, method, N, rectilinear, fma>" after a fused evaluation.
+ * Scratch   both paths work in one of the handle's scratch blocks (records: 16 to 64 bytes per axis coordinate; the
+ *           expanded slice), under the rules of interpn_hip_eval_device_ex: one block per concurrent stream, at most 4,
+ *           allocated on first use unless INTERPN_HIP_EVAL_NO_ALLOC is given; interpn_hip_reserve_lattice provides
+ *           them in advance.  Without a block the call returns INTERPN_HIP_ERR_OUT_OF_MEMORY.  A stream under graph
+ *           capture never allocates and touches no event of a block: reserve or evaluate once before capturing, and keep
+ *           other streams away from the handle while the graph replays.
+ * Checks    h, axes, axis_lens, out or an axes[d] NULL: INTERPN_HIP_ERR_INVALID_ARGUMENT; interpn::one_dim handles:
+ *           INTERPN_HIP_ERR_UNSUPPORTED; naxes != ndims: what interpn_hip_eval_device returns for the wrong number of
+ *           coordinate arrays; a point count beyond size_t: INTERPN_HIP_ERR_INVALID_ARGUMENT; more than 2^31 axis
+ *           coordinates in all: INTERPN_HIP_ERR_UNSUPPORTED; any axis_lens[d] == 0: no points, INTERPN_HIP_OK, nothing
+ *           written.
+ * Failing   regular grids only (rectilinear grids never fail a point and propagate NaN): a coordinate the reference
+ * points    cannot convert (NaN, +-inf, |floc| >= 2^63) at position j of axis d fails every lattice point that uses it.
+ *           interpn_hip_finish reports the reference loop's first failure in C order,
+ *           min over bad (d, j) of j * prod(axis_lens[e], e > d), with the handle's status for such points.
+ * ---------------------------------------------------------------------------------------- */
+enum { INTERPN_HIP_LATTICE_PATH_FUSED = 0, INTERPN_HIP_LATTICE_PATH_EXPANDED = 1 };
+/* Asynchronous on `stream`.  `axes`: HOST array of `naxes` DEVICE pointers, axes[d] to axis_lens[d] coordinates; `out`: device,
+ * prod(axis_lens) elements.  `flags`: INTERPN_HIP_EVAL_NO_ALLOC.  *path_taken (may be NULL): INTERPN_HIP_LATTICE_PATH_*. */
+int interpn_hip_eval_lattice_device(interpn_hip_interp* h, const void* const* axes, const size_t* axis_lens, size_t naxes,
+                                    void* out, void* stream, unsigned flags, int* path_taken);
+/* The same on host arrays, synchronous (chunks of leading-axis indices, 2^25 points each).  On a failing point the status
+ * is the handle's ("Unrepresentable coordinate value"), exactly out[0..first_bad) is written, the rest of `out` is left
+ * as it was, and *first_bad_index (may be NULL) receives the index.  Shares the sticky status word with the device form:
+ * finish device evaluations first. */
+int interpn_hip_eval_lattice_host(interpn_hip_interp* h, const void* const* axes, const size_t* axis_lens, size_t naxes,
+                                  void* out, uint64_t* first_bad_index);
+/* Scratch blocks for lattices of up to these axis lengths on up to `nstreams` concurrent streams, whichever path the
+ * options choose at evaluation time.  Synchronous.  (An expanded slice that the handle would sort or sweep takes a
+ * second block: interpn_hip_reserve; without one it is evaluated in place.) */
+int interpn_hip_reserve_lattice(interpn_hip_interp* h, const size_t* axis_lens, size_t naxes, int nstreams);
+/* Which path a lattice of `axis_lens` on a grid of `dims` takes in automatic mode on an MI355X, the fused workgroup's
+ * LDS bytes (0 when expanded) and the overflow-checked point count.  Needs no device; honours the INTERPN_HIP_*
+ * variables a new handle would latch (AXIS_LDS_KB, LATTICE, FORCE_GENERIC).  `method`: INTERPN_HIP_LINEAR / _CUBIC /
+ * _NEAREST.  INTERPN_HIP_ERR_INVALID_ARGUMENT: element size, method, ndims outside 1..8, an axis below the method's
+ * minimum, a point count beyond size_t. */
+int interpn_hip_lattice_plan(size_t elem_size, int method, size_t ndims, const size_t* dims, const size_t* axis_lens,
+                             int* path, size_t* lds_bytes, size_t* npoints);
+
 #ifdef __cplusplus
 }
 #endif

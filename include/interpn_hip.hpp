@@ -247,6 +247,22 @@ class Handle {
     return st == INTERPN_HIP_OK ? Result<T>::Ok(out) : Result<T>::Err(st);
   }
 
+  // `interp_lattice` (not in the crate): the points are the tensor product axes[0] x .. x axes[N-1] of one coordinate
+  // vector per grid axis; out[i_0, .., i_{N-1}] in C order, out.len() = the product of the vectors' lengths, else
+  // "Dimension mismatch".  The bits of `interp` on the expanded points, which are never materialised
+  // (interpn_hip_eval_lattice_host).  Aborts like `interp` at the first point with an unrepresentable coordinate.
+  Result<void> interp_lattice(const std::array<Slice<T>, N>& axes, SliceMut<T> out) const {
+    Unpacked<T> a(axes);
+    std::size_t want = 1;
+    for (std::size_t d = 0; d < N; ++d) {
+      if (a.lens[d] != 0 && want > static_cast<std::size_t>(-1) / a.lens[d]) return Result<void>::from(INTERPN_HIP_ERR_DIM_MISMATCH);
+      want *= a.lens[d];
+    }
+    if (out.len() != want) return Result<void>::from(INTERPN_HIP_ERR_DIM_MISMATCH);
+    return Result<void>::from(interpn_hip_eval_lattice_host(h_, reinterpret_cast<const void* const*>(a.ptrs.data()), a.lens.data(), N,
+                                                            out.ptr, nullptr));
+  }
+
   // Escape hatch to the C ABI (device-pointer evaluation on a stream, options, kernel name ...).
   interpn_hip_interp* raw() const { return h_; }
 

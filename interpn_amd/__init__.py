@@ -40,6 +40,8 @@ __all__ = [
     "raw",
     "interpn",
     "interpn_fields",
+    "interpn_lattice",
+    "lattice_plan",
     "Fields",
     "fields_layout",
     "Interpolator",
@@ -174,6 +176,101 @@ def _interpn_on_device(obs, grids, vals, method, out, linearize_extrapolation, a
     finally:
         it.close()
     return out_t.reshape(shape)
+
+
+def interpn_lattice(
+    axes: Sequence,
+    grids: Sequence,
+    vals,
+    *,
+    method: Literal["linear", "cubic", "nearest"] = "linear",
+    out=None,
+    linearize_extrapolation: bool = True,
+    assume_regular: bool = False,
+    check_bounds: bool = False,
+    bounds_atol: float = 1e-8,
+):
+    """`interpn()` on the lattice axes[0] x .. x axes[N-1]: one coordinate vector per grid axis instead of N arrays of
+    expanded points.  Returns an array (a tensor, if the vectors are torch CUDA tensors) of shape
+    `tuple(len(a) for a in axes)` whose element [i_0, .., i_{N-1}] is the interpolant at (axes[0][i_0], ..,
+    axes[N-1][i_{N-1}]) — the bits of `interpn(np.meshgrid(*axes, indexing="ij"), ...)`, without the meshgrid.
+
+    The rules are those of `interpn()`: inputs ravelled, dtype from `vals`, regular iff every spacing is exactly equal or
+    `assume_regular`.  `check_bounds` checks the N vectors (a lattice is inside the grid exactly when each axis is)."""
+    if method not in ("linear", "cubic", "nearest"):
+        raise ValueError(f"Unsupported interpolation configuration: {method}")
+    axes = list(axes)
+    grids = [np.ascontiguousarray(np.asarray(x).ravel()) for x in grids]
+    if len(axes) != len(grids):
+        raise ValueError(f"axes: expected {len(grids)} coordinate vectors (one per grid axis), got {len(axes)}")
+    on_device = bool(axes) and _is_cuda_tensor(axes[0])
+    if not (_is_cuda_tensor(vals) or isinstance(vals, np.ndarray)):
+        raise TypeError("argument 'vals': expected a numpy array or a torch tensor")
+    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
+    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
+    vals = vals.reshape(-1).contiguous() if _is_cuda_tensor(vals) else np.ascontiguousarray(vals.ravel())
+    grids = [g.astype(dtype, copy=False) for g in grids]
+    shape = tuple(int(a.numel()) if _is_cuda_tensor(a) else int(np.asarray(a).size) for a in axes)
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+    device = -1
+    if on_device:
+        import torch
+
+        device = axes[0].device.index if axes[0].device.index is not None else torch.cuda.current_device()
+        axes = [a.reshape(-1).contiguous() for a in axes]
+    else:
+        axes = [np.ascontiguousarray(np.asarray(a).ravel()) for a in axes]
+    if assume_regular or _check_regular(grids):
+        starts = np.array([g[0] for g in grids], dtype=dtype)
+        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
+        it = Interpolator.regular(method, [len(g) for g in grids], starts, steps, vals,
+                                  linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
+    else:
+        it = Interpolator.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation,
+                                      device=device, dtype=dtype)
+    try:
+        if check_bounds:
+            # N short batches: axis d is checked against dimension d with the other coordinates held at the grid's origin
+            import torch
+
+            dev = torch.device("cuda", it.device())
+            tdt = torch.float64 if dtype == np.float64 else torch.float32
+            for d, a in enumerate(axes):
+                a_t = a if on_device else torch.from_numpy(a).to(dev)
+                if a_t.numel() == 0:
+                    continue
+                batch = [a_t if e == d else torch.full((a_t.numel(),), float(grids[e][0]), dtype=tdt, device=dev)
+                         for e in range(len(grids))]
+                if it.check_bounds_tensors(batch, bounds_atol)[d]:
+                    raise ValueError("Observation points violate interpolator bounds")
+        if on_device:
+            res = it.eval_lattice_tensors(axes, out)
+            it.finish()
+        else:
+            res = it.eval_lattice_host(axes, out)
+    finally:
+        it.close()
+    return res
+
+
+def lattice_plan(dtype, method: str, dims, axis_lens):
+    """(path, lds_bytes, npoints): the path ("fused" / "expanded") a lattice of `axis_lens` coordinates per axis takes in
+    automatic mode on a grid of `dims`, the LDS bytes of the fused kernel's workgroup and the point count
+    (`interpn_hip_lattice_plan`; needs no device)."""
+    import ctypes
+
+    from .raw import _dims
+
+    d, nd = _dims(dims)
+    m, nm = _dims(axis_lens)
+    if nd != nm:
+        raise ValueError(f"axis_lens: expected {nd} lengths, got {nm}")
+    path, lds, npts = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    st = _lib.load().interpn_hip_lattice_plan(np.dtype(dtype).itemsize, _lib.METHODS[method], nd, d, m, ctypes.byref(path),
+                                              ctypes.byref(lds), ctypes.byref(npts))
+    _lib.raise_for_status(st)
+    return _lib.LATTICE_PATHS[path.value], int(lds.value), int(npts.value)
 
 
 def _check_regular(grids) -> bool:

@@ -33,6 +33,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 FLAVOUR_FMA, FLAVOUR_NO_FMA = 0x100, 0x200  # OR-ed into `method` of interpn_hip_create_*
 PATH_IN_PLACE, PATH_BINNED, PATH_SWEEP = 0, 1, 2
 FIELDS_PATH_FUSED, FIELDS_PATH_PER_FIELD = 0, 1  # interpn_hip_fields_eval_device
+LATTICE_PATH_FUSED, LATTICE_PATH_EXPANDED = 0, 1  # interpn_hip_eval_lattice_device
+LATTICE_PATHS = {LATTICE_PATH_FUSED: "fused", LATTICE_PATH_EXPANDED: "expanded"}
 EVAL_NO_ALLOC = 1
 WHY = {0: "", 1: "batch below the break-even size or option binned = 0", 2: "stream under graph capture",
        3: "no reserved scratch block free and allocation not allowed", 4: "scratch allocation failed",
@@ -171,6 +173,13 @@ def load() -> ctypes.CDLL:
     lib.interpn_hip_fields_get_option.argtypes = [c_void_p, c_char_p, POINTER(ctypes.c_longlong)]
     lib.interpn_hip_fields_layout.argtypes = [c_size_t, c_size_t, POINTER(c_size_t), c_size_t, POINTER(c_int), POINTER(c_size_t),
                                               POINTER(c_size_t)]
+    lib.interpn_hip_eval_lattice_device.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_void_p,
+                                                    ctypes.c_uint, POINTER(c_int)]
+    lib.interpn_hip_eval_lattice_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p,
+                                                  POINTER(c_uint64)]
+    lib.interpn_hip_reserve_lattice.argtypes = [c_void_p, POINTER(c_size_t), c_size_t, c_int]
+    lib.interpn_hip_lattice_plan.argtypes = [c_size_t, c_int, c_size_t, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_int),
+                                             POINTER(c_size_t), POINTER(c_size_t)]
     _lib = lib
     return lib
 

@@ -77,6 +77,20 @@ class _Base:
         self.eval_unchecked(obs, out_inner)
         return out_inner
 
+    def eval_lattice(self, axes, out=None):
+        """Evaluate on the lattice axes[0] x .. x axes[N-1] (one coordinate vector per grid axis, numpy arrays or torch
+        CUDA tensors like `eval`): the result has shape `tuple(len(a) for a in axes)` and the bits of `eval` on the
+        `meshgrid(..., indexing="ij")` of the vectors, which is never materialised."""
+        axes = list(axes)
+        if axes and _is_tensor(axes[0]):
+            res = self._interp().eval_lattice_tensors([a.reshape(-1).contiguous() for a in axes], out)
+            self._interp().finish()
+            return res
+        dtype = self.vals.dtype
+        if dtype not in (np.float64, np.float32):
+            raise TypeError(f"Unexpected data type: {dtype}")
+        return self._interp().eval_lattice_host([np.ascontiguousarray(np.asarray(a).ravel()) for a in axes], out)
+
     def eval_unchecked(self, obs, out=None):
         dtype = self.vals.dtype
         if dtype not in (np.float64, np.float32):

@@ -60,6 +60,7 @@ struct LaunchConfig {
   int gated_iters = 4;     // rows of 256 lanes per workgroup of the gated brick launch behind an automatic sweep launch (an empty workgroup costs dispatch time)
   int sweep_probe = 2;     // automatic sweep launches: sample the batch on the device first and let the one-pass kernel take coherent batches — 0: never (the sweep kernel whatever the points look like), 1: every launch, 2: every launch until three samples in a row came out unordered, then every 16th (abi_sweep.hip)
   // (sweep itself: -1 automatic, 0 never, 1 always, 2 always with the sample deciding between the two kernels)
+  int lattice = -1;        // lattice evaluation (lattice.h): -1 the row kernel where the layout rules of lattice_plan say it pays, 0 never (expand and evaluate), 1 wherever it is covered and its lines fit the LDS budget
   int sweep_period = 0;    // sweep evaluation: ticks of 10 ns per sweep of the leading index (0: what the previous launch measured; 1: no clock, rows in sorted order; tests / tuning)
 };
 
@@ -179,6 +180,7 @@ struct GridDesc {
   size_t od_g_off = 0, od_tab_off = 0, od_table_bytes = 0;
   LaunchConfig cfg;
   mutable KernelTag tag;
+  mutable int last_lattice_path = -1;  // the most recent lattice evaluation: INTERPN_HIP_LATTICE_PATH_*, -1 before any
   mutable int last_binned = 0;  // the most recent device-pointer evaluation sorted its points first (binned evaluation)
 };
 

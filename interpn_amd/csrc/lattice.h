@@ -1,0 +1,117 @@
+// Lattice evaluation: the observation points are the tensor product of N coordinate vectors (one per axis), results in
+// C order with the last axis contiguous — re-gridding, `RegularGridInterpolator` on a meshgrid, refining a table.
+//
+// What a lattice shares between its points:
+//   * everything the reference derives from ONE coordinate of ONE axis — cell index, normalized coordinate, the cubic
+//     saturation class, the rectilinear spacing ratios — exists sum(m_d) times, not prod(m_d) * N times.  k_lattice_axes
+//     computes it once per axis coordinate with the device functions the per-point kernels use (interpn_device.h) and
+//     stores it as a record (below).
+//   * the reference reduces dimension 0 first and dimension N-1 last (multilinear/regular.rs:366-403,
+//     multicubic/regular.rs:368-421).  For one output row (all lattice indices but the last fixed) the partial results
+//     after dims 0..N-2 depend only on the grid column k of the last axis: r[k], k < n_{N-1}.  k_lattice_rows computes
+//     that line once per row into LDS; every output of the row is then ONE node of the last dimension over
+//     r[loc .. loc + 1] (linear) or r[loc .. loc + 3] (cubic).  Operations and operands are those of interp_one, in its
+//     order: the bits are the per-point kernels'.
+//
+// Traffic model of the row kernel (per output row, T = element type, F = 2 linear / 4 cubic, n = n_{N-1} grid points and
+// m = m_{N-1} lattice coordinates along the last axis): F^(N-1) coalesced reads of n elements of the C-ordered `vals`
+// (table rows that the rows in flight share: L2 hits), m record reads (16 to 64 bytes, the same m records for every row:
+// L2 hits), m result stores — the only stream that reaches HBM: sizeof(T) per point against (N + 1) sizeof(T) for the
+// per-point kernels on an expanded lattice.  Nodes: (F^(N-1) - 1) / (F - 1) per grid column plus one per point, instead
+// of (F^N - 1) / (F - 1) per point.
+//
+// Launch shape: 256-thread persistent workgroups, ONE ROW PER WAVE (the row's records of dims 0..N-2 are wave-uniform
+// and come through the scalar unit; a wave synchronises with itself only), four LDS lines per workgroup.
+#pragma once
+
+#include "interpn_device.h"
+#include "interpn_host.h"
+
+namespace interpn {
+
+constexpr int kLatticeWaves = 4;                 // waves (= rows in flight, = LDS lines) per workgroup
+constexpr int kLatticeBlock = 64 * kLatticeWaves;
+constexpr size_t kLatticeMaxCoords = (size_t)1 << 31;  // sum of the axis lengths a call accepts (records and flags are indexed with 32 bits)
+
+// Per-coordinate records.  `cls` = Sat | linear << 2 (linear: outside the grid under linearize_extrapolation).
+template <typename T> struct LatticeRecLinear { T t; int loc; };
+template <typename T> struct LatticeRecCubic { T tt; int loc; int cls; };
+template <typename T> struct LatticeRecCubicRect { T t, r0, a0, c0, r1, a1, c1; int loc; int cls; };
+
+template <typename T, int METHOD, bool RECT> struct LatticeRec { typedef LatticeRecLinear<T> type; };
+template <typename T> struct LatticeRec<T, kCubic, false> { typedef LatticeRecCubic<T> type; };
+template <typename T> struct LatticeRec<T, kCubic, true> { typedef LatticeRecCubicRect<T> type; };
+
+inline size_t lattice_record_bytes(int method, int kind, size_t elem) {
+  if (method == kLinear) return elem == 8 ? sizeof(LatticeRecLinear<double>) : sizeof(LatticeRecLinear<float>);
+  if (kind == kRegular) return elem == 8 ? sizeof(LatticeRecCubic<double>) : sizeof(LatticeRecCubic<float>);
+  return elem == 8 ? sizeof(LatticeRecCubicRect<double>) : sizeof(LatticeRecCubicRect<float>);
+}
+
+// One LDS line of the row kernel: n_{N-1} elements, rounded up to 16 bytes.
+inline size_t lattice_line_bytes(size_t n_last, size_t elem) { return (n_last * elem + 15) & ~(size_t)15; }
+
+enum LatticeMode : int { kLatticeAuto = -1, kLatticeNever = 0, kLatticeFused = 1 };
+
+// Which path a lattice takes.  `covered`: the row kernel exists for (method, N); `fits`: its four lines fit `budget` bytes
+// of LDS.  Automatic mode adds the two layout rules of DESIGN.md ("Lattice evaluation"):
+//   rows   a wave owns a row, so a lattice needs rows to fill the device: prod(m_0 .. m_{N-2}) >= 4 waves x num_cus;
+//   last   a row costs F^(N-1) reads per GRID column before its first output: n_{N-1} <= 4 max(m_{N-1}, 64).
+struct LatticePlan {
+  bool covered = false, fits = false, fused = false;
+  size_t lds_bytes = 0;    // of a workgroup on the fused path (0 otherwise)
+  size_t nrows = 0;        // prod(m_0 .. m_{N-2})
+};
+inline LatticePlan lattice_plan(int method, int ndims, size_t elem, const int* n, const size_t* m, size_t budget, int num_cus,
+                                int mode) {
+  LatticePlan p;
+  p.covered = (method == kLinear || method == kCubic) && (ndims == 2 || ndims == 3);
+  if (!p.covered) return p;
+  const size_t n_last = (size_t)n[ndims - 1], m_last = m[ndims - 1];
+  const size_t lds = (size_t)kLatticeWaves * lattice_line_bytes(n_last, elem);
+  p.fits = lds <= budget;
+  p.nrows = 1;
+  for (int d = 0; d + 1 < ndims; ++d) p.nrows *= m[d];
+  bool fused = p.fits && mode != kLatticeNever;
+  for (int d = 0; d < ndims; ++d) fused = fused && m[d] < ((size_t)1 << 31);
+  if (fused && mode == kLatticeAuto) {
+    const size_t wide = m_last > 64 ? m_last : 64;
+    fused = p.nrows >= (size_t)kLatticeWaves * (size_t)num_cus && n_last <= 4 * wide;
+  }
+  p.fused = fused;
+  p.lds_bytes = fused ? lds : 0;
+  return p;
+}
+
+// The LDS budget of the row kernel's lines: what the handle already grants rectilinear axis images
+// (Thresholds::axis_lds, or option "axis_lds_kb").
+inline size_t lattice_lds_budget(const LaunchConfig& c) {
+  return c.axis_lds_kb >= 0 ? (size_t)c.axis_lds_kb * 1024 : thresholds(c).axis_lds;
+}
+
+// The lattice as the kernels see it (host arrays of at most kMaxDims entries).
+struct LatticeShape {
+  int ndims = 0;
+  const void* axes[8] = {nullptr};   // device
+  size_t m[8] = {0};
+  unsigned rec_off[8] = {0};         // index of axis d's first record / flag: sum of m[0 .. d)
+  unsigned long long weight[8] = {0};  // prod of m[e], e > d: the flat index step of axis d
+  size_t coords = 0;                 // sum of m
+  size_t npoints = 0;
+};
+
+// k_lattice.hip
+// Records of every axis coordinate into `recs` (lattice_record_bytes each; fused path), and on regular grids the
+// bad-coordinate flags (`bad`, one byte per coordinate, may be null) with the atomicMin of the flat index of the first
+// failing lattice point into `first_bad`.  `recs` null: flags and first_bad only (expanded path; every method).
+hipError_t launch_lattice_axes(const GridDesc& g, const LatticeShape& s, void* recs, unsigned char* bad,
+                               unsigned long long* first_bad, hipStream_t stream);
+hipError_t launch_lattice_rows(const GridDesc& g, const LatticeShape& s, const void* recs, void* out, size_t lds_bytes,
+                               hipStream_t stream);
+// SoA coordinates of the lattice points [begin, begin + count) into dst[d][0 .. count); a coordinate flagged in `bad`
+// (may be null) is replaced by the grid's first coordinate, so that the evaluation of the slice never reports a
+// slice-relative failing index (the axes kernel has reported the lattice's).
+hipError_t launch_lattice_expand(const GridDesc& g, const LatticeShape& s, const unsigned char* bad, void* const* dst,
+                                 size_t begin, size_t count, hipStream_t stream);
+
+}  // namespace interpn

@@ -273,6 +273,85 @@ class Interpolator:
         self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
         return out
 
+    # -- lattice evaluation (points = tensor product of one coordinate vector per axis) ----
+    @property
+    def last_lattice_path(self):
+        """"fused" or "expanded": what the most recent lattice evaluation did (None before any)."""
+        return _lib.LATTICE_PATHS.get(self.get_option("last_lattice_path"))
+
+    def reserve_lattice(self, axis_lens, nstreams: int = 1) -> None:
+        """Pre-allocate the scratch of lattice evaluations with up to these axis lengths on up to `nstreams`
+        concurrent streams (`interpn_hip_reserve_lattice`); afterwards they work with `no_alloc=True`."""
+        lens, n = _dims(axis_lens)
+        _lib.raise_for_status(_lib.load().interpn_hip_reserve_lattice(self._h, lens, n, int(nstreams)))
+
+    def eval_lattice_host(self, axes, out: np.ndarray = None) -> np.ndarray:
+        """Evaluate on the lattice axes[0] x .. x axes[N-1] of host coordinate vectors (synchronous): the result has
+        shape `tuple(len(a) for a in axes)` and equals `eval_host` on `np.meshgrid(*axes, indexing="ij")`, bit for bit
+        (`interpn_hip_eval_lattice_host`).  On "Unrepresentable coordinate value" the AssertionError carries
+        `first_bad_index` (C order) and exactly the results in front of it have been written."""
+        lib = _lib.load()
+        aptr, alen, naxes, _keep = _slice_of_slices("axes", axes, self.dtype)
+        shape = tuple(int(alen[i]) for i in range(naxes))
+        if out is None:
+            out = np.zeros(shape, dtype=self.dtype)
+        if not isinstance(out, np.ndarray):
+            raise TypeError(f"argument 'out': expected a numpy array, got {type(out).__name__}")
+        if out.dtype != self.dtype:
+            raise TypeError(f"argument 'out': expected dtype {self.dtype.name}, got {out.dtype.name}")
+        if naxes == self._ndims and out.shape != shape and out.shape != (int(np.prod(shape, dtype=object)),):
+            raise ValueError(f"out: expected shape {shape}, got {out.shape}")
+        if not out.flags.c_contiguous:
+            raise ValueError("argument 'out': The given array is not contiguous")
+        if not out.flags.writeable:
+            raise ValueError("argument 'out': array is read-only")
+        vp = (c_void_p * max(naxes, 1))()
+        for i in range(naxes):
+            vp[i] = ctypes.cast(aptr[i], c_void_p)
+        bad = c_uint64(0)
+        st = lib.interpn_hip_eval_lattice_host(self._h, vp, alen, naxes, out.ctypes.data_as(c_void_p), ctypes.byref(bad))
+        if st in _lib.UNREPRESENTABLE:
+            err = AssertionError(_lib.strerror(st))
+            err.first_bad_index = bad.value
+            raise err
+        _lib.raise_for_status(st)
+        return out
+
+    def eval_lattice_tensors(self, axes, out=None, stream=None, no_alloc: bool = False):
+        """The same on torch CUDA tensors: `axes` are contiguous 1-D tensors of the handle's dtype, the result a tensor of
+        shape `tuple(len(a) for a in axes)`.  Asynchronous like `eval_tensors`; `finish()` synchronises and raises
+        for a coordinate the reference cannot evaluate, with `first_bad_index` in C order.  `.last_lattice_path` says
+        which path ran (`interpn_hip_eval_lattice_device`)."""
+        import torch
+
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        axes = list(axes)
+        for i, t in enumerate(axes):
+            if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
+                raise TypeError(f"axes[{i}]: expected a contiguous 1-D {want} CUDA tensor")
+            self._check_same_device(f"axes[{i}]", t)
+        shape = tuple(int(t.numel()) for t in axes)
+        count = int(np.prod(shape, dtype=object)) if shape else 0
+        if out is None:
+            out = torch.empty(shape, dtype=want, device=torch.device("cuda", self.device()))
+        elif not (out.is_cuda and out.is_contiguous() and out.dtype == want):
+            raise TypeError(f"out: expected a contiguous {want} CUDA tensor")
+        elif len(axes) == self._ndims and tuple(out.shape) != shape and tuple(out.shape) != (count,):
+            raise ValueError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+        else:
+            self._check_same_device("out", out)
+        owner = torch.cuda.current_stream(self.device()) if stream is None else stream
+        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        n = len(axes)
+        vp = (c_void_p * max(n, 1))(*[t.data_ptr() for t in axes])
+        lens = (c_size_t * max(n, 1))(*shape)
+        path = ctypes.c_int(0)
+        st = _lib.load().interpn_hip_eval_lattice_device(self._h, vp, lens, n, c_void_p(out.data_ptr()), c_void_p(int(raw)),
+                                                         _lib.EVAL_NO_ALLOC if no_alloc else 0, ctypes.byref(path))
+        _lib.raise_for_status(st)
+        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        return out
+
     def check_bounds_tensors(self, obs, atol: float, stream=None) -> np.ndarray:
         """`check_bounds` on torch CUDA tensors against this interpolator's grid: one flag per
         dimension, True where any coordinate lies outside the grid by `atol` or more
