@@ -122,7 +122,8 @@ typedef enum interpn_hip_status {
   INTERPN_HIP_ERR_UNREPRESENTABLE_NUMBER = 12, /* "Unrepresentable number"              one_dim/mod.rs:111 */
   /* statuses of this implementation */
   INTERPN_HIP_ERR_INVALID_ARGUMENT = 32, /* null pointer, unknown enum value, dtype mismatch */
-  INTERPN_HIP_ERR_UNSUPPORTED = 33,      /* axis longer than 2^31-257 points (f32: 2^24) */
+  INTERPN_HIP_ERR_UNSUPPORTED = 33,      /* axis longer than 2^31-257 points (f32: 2^24); interpn_hip_eval_grad_* on a handle
+                                            that is not multilinear (multicubic, nearest, interpn::one_dim) */
   INTERPN_HIP_ERR_NO_DEVICE = 34,        /* no usable HIP device */
   INTERPN_HIP_ERR_OUT_OF_MEMORY = 35,    /* device or pinned-host allocation failed */
   INTERPN_HIP_ERR_HIP = 36               /* any other HIP runtime failure (see interpn_hip_last_hip_error) */
@@ -327,6 +328,34 @@ int interpn_hip_eval_device_sharded(interpn_hip_interp* const* handles, size_t n
  * 1 always for N = 2..4).  Results and the first-failing-index contract are unchanged. */
 int interpn_hip_eval_device(interpn_hip_interp* h, const void* const* obs, size_t nobs, void* out,
                             size_t npoints, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Value and gradient of a MULTILINEAR handle: out[i] = f(x_i) with the bits of interpn_hip_eval_*, and
+ * grad[d][i] = df/dx_d at x_i, the derivative of the interpolant with respect to the observation coordinates, from the
+ * 2^N corner values the value is made of (one pass over the points, no table traffic beyond a value call's).
+ * The reference has no gradient; the definition (DESIGN.md "Gradients") is, per point and at the handle's fma flavour,
+ * with the cell origin, the normalised coordinates t[] and the corners V[c] (bit d of c = offset along dimension d) of
+ * the value path and lerp(t, y0, y1) the reference's step (dy = y1 - y0; t.mul_add(dy, y0) or y0 + t * dy):
+ *   W[c']   = V[c' | 1 << d] - V[c']   for the 2^(N-1) corners c' with bit d clear
+ *   s       = W reduced over the dimensions e != d in ascending e with lerp(t[e], lower, upper) (N = 1: s = W[0])
+ *   grad[d] = s / h[d]                 h[d] = steps[d], or x1 - x0 of the point's cell on a rectilinear grid
+ * every operation rounded in the element type.  It is the slope of the cell the value path selects: outside the grid
+ * the edge cell's (the slope of the linear extrapolation), at a knot that of the side the reference's cell rule picks;
+ * non-finite inputs propagate.
+ *   grad     HOST array of `nobs` pointers, each to `npoints` (`nout`) elements: device pointers in the device form,
+ *            host pointers in the host form; grad[d] receives component d.  `out` is required.
+ * Checks and statuses are those of interpn_hip_eval_device / _host ("Dimension mismatch"; INTERPN_HIP_ERR_INVALID_ARGUMENT
+ * for h, obs, out, grad or one of their entries NULL); a handle of any other method (multicubic, nearest,
+ * interpn::one_dim) returns INTERPN_HIP_ERR_UNSUPPORTED before any device work.
+ * The device form is ONE kernel for every batch size (no copy, no synchronisation, no allocation: capturable into a
+ * graph), reported by interpn_hip_kernel_name: "interpn::k_linear_grad<...>" for N = 2, 3 on the handle's re-laid table,
+ * "interpn::k_linear_grad_n<...>" (runtime N on the C-ordered grid) for N = 1, N = 4..8, handles without a table and
+ * option force_generic.  INTERPN_HIP_ERR_UNREPRESENTABLE keeps the first-failing-index contract: the host form writes
+ * out[0..i) and grad[d][0..i) and leaves the rest untouched; the device form reports i through interpn_hip_finish. */
+int interpn_hip_eval_grad_device(interpn_hip_interp* h, const void* const* obs, size_t nobs, void* out,
+                                 void* const* grad, size_t npoints, void* stream);
+int interpn_hip_eval_grad_host(interpn_hip_interp* h, const void* const* obs, const size_t* obs_lens, size_t nobs,
+                               void* out, size_t nout, void* const* grad);
 
 /* The same evaluation, telling the caller which path it took.
  *   flags        INTERPN_HIP_EVAL_NO_ALLOC: never allocate (scratch that interpn_hip_reserve has

@@ -40,6 +40,7 @@ __all__ = [
     "raw",
     "interpn",
     "interpn_fields",
+    "interpn_grad",
     "interpn_lattice",
     "lattice_plan",
     "Fields",
@@ -176,6 +177,72 @@ def _interpn_on_device(obs, grids, vals, method, out, linearize_extrapolation, a
     finally:
         it.close()
     return out_t.reshape(shape)
+
+
+def interpn_grad(
+    obs: Sequence,
+    grids: Sequence,
+    vals,
+    *,
+    assume_regular: bool = False,
+    check_bounds: bool = False,
+    bounds_atol: float = 1e-8,
+):
+    """Multilinear value and gradient at the observation points in one pass: returns `(out, grad)`, `out` shaped like
+    `obs[0]` with the bits of `interpn(obs, grids, vals, method="linear")`, `grad` of shape `(N, *obs[0].shape)` with
+    `grad[d]` the derivative of the interpolant with respect to coordinate d — the slope of the cell the value uses
+    (outside the grid: of the linear extrapolation).  Arrays for numpy points, tensors for torch CUDA points.
+
+    The rules are those of `interpn()`: inputs ravelled, dtype from `vals`, regular iff every spacing is exactly equal or
+    `assume_regular`.  Linear only: the multicubic gradient is not built."""
+    obs = list(obs)
+    grids = [np.ascontiguousarray(np.asarray(x).ravel()) for x in grids]
+    on_device = bool(obs) and _is_cuda_tensor(obs[0])
+    if not (_is_cuda_tensor(vals) or isinstance(vals, np.ndarray)):
+        raise TypeError("argument 'vals': expected a numpy array or a torch tensor")
+    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
+    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
+    vals = vals.reshape(-1).contiguous() if _is_cuda_tensor(vals) else np.ascontiguousarray(vals.ravel())
+    grids = [g.astype(dtype, copy=False) for g in grids]
+    shape = tuple(obs[0].shape) if obs else (0,)
+    device = -1
+    if on_device:
+        import torch
+
+        device = obs[0].device.index if obs[0].device.index is not None else torch.cuda.current_device()
+        flat = [x.reshape(-1).contiguous() for x in obs]
+    else:
+        flat = [np.ascontiguousarray(np.asarray(x).ravel()) for x in obs]
+    is_regular = assume_regular or _check_regular(grids)
+    if is_regular:
+        dims = [len(g) for g in grids]
+        starts = np.array([g[0] for g in grids], dtype=dtype)
+        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
+        it = Interpolator.regular("linear", dims, starts, steps, vals, device=device, dtype=dtype)
+    else:
+        it = Interpolator.rectilinear("linear", grids, vals, device=device, dtype=dtype)
+    try:
+        if check_bounds:
+            if on_device:
+                violated = it.check_bounds_tensors(flat, bounds_atol).any()
+            else:
+                sfx = "f64" if dtype == np.float64 else "f32"
+                outb = np.zeros(len(grids), dtype=bool)
+                if is_regular:
+                    getattr(raw, f"check_bounds_regular_{sfx}")(dims, starts, steps, flat, bounds_atol, outb)
+                else:
+                    getattr(raw, f"check_bounds_rectilinear_{sfx}")(grids, flat, bounds_atol, outb)
+                violated = any(outb)
+            if violated:
+                raise ValueError("Observation points violate interpolator bounds")
+        if on_device:
+            out, grad = it.eval_grad_tensors(flat)
+            it.finish()
+        else:
+            out, grad = it.eval_grad_host(flat)
+    finally:
+        it.close()
+    return out.reshape(shape), grad.reshape((len(flat),) + shape)
 
 
 def interpn_lattice(

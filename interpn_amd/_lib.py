@@ -24,6 +24,7 @@ ERR_LENGTH_MISMATCH = 11          # "Length mismatch" (one_dim)
 ERR_UNREPRESENTABLE_NUMBER = 12   # "Unrepresentable number" (one_dim, regular grids)
 UNREPRESENTABLE = (ERR_UNREPRESENTABLE, ERR_UNREPRESENTABLE_NUMBER)  # statuses that carry a first failing index
 ERR_INVALID_ARGUMENT = 32
+ERR_UNSUPPORTED = 33
 
 LINEAR, CUBIC, NEAREST = 0, 1, 2
 METHODS = {"linear": LINEAR, "cubic": CUBIC, "nearest": NEAREST}
@@ -143,6 +144,10 @@ def load() -> ctypes.CDLL:
     lib.interpn_hip_eval_device.argtypes = [c_void_p, POINTER(c_void_p), c_size_t, c_void_p, c_size_t, c_void_p]
     lib.interpn_hip_eval_device_ex.argtypes = [c_void_p, POINTER(c_void_p), c_size_t, c_void_p, c_size_t, c_void_p,
                                                ctypes.c_uint, POINTER(c_int), POINTER(c_int)]
+    lib.interpn_hip_eval_grad_device.argtypes = [c_void_p, POINTER(c_void_p), c_size_t, c_void_p, POINTER(c_void_p), c_size_t,
+                                                 c_void_p]
+    lib.interpn_hip_eval_grad_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_size_t,
+                                               POINTER(c_void_p)]
     lib.interpn_hip_reserve.argtypes = [c_void_p, c_size_t, c_int]
     lib.interpn_hip_stage_ms.argtypes = [c_void_p, POINTER(c_double), c_size_t]
     lib.interpn_hip_check_bounds_device.argtypes = [c_void_p, POINTER(c_void_p), c_size_t, c_size_t, ctypes.c_double,

@@ -1,0 +1,50 @@
+"""A multilinear `Interpolator` as a differentiable function of the observation coordinates.
+
+`interp(it, obs)` evaluates `it` at the points given as torch CUDA tensors and takes part in torch's autograd: the
+backward pass multiplies the incoming gradient by the derivative of the interpolant with respect to each coordinate,
+which the forward pass computed in the same kernel (`Interpolator.eval_grad_tensors`).  The table is a constant of the
+graph: the gradient with respect to `vals` is not built.
+
+torch is imported on first use, and this module is not imported by `import interpn_amd`.
+"""
+
+from __future__ import annotations
+
+_FUNCTION = None
+
+
+def _function():
+    """The torch.autograd.Function, built on first use so that importing this module does not import torch."""
+    global _FUNCTION
+    if _FUNCTION is not None:
+        return _FUNCTION
+    import torch
+
+    class _Interp(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, it, *obs):
+            shape = obs[0].shape
+            flat = [o.detach().reshape(-1).contiguous() for o in obs]
+            out, grad = it.eval_grad_tensors(flat)
+            it.finish()
+            ctx.save_for_backward(grad)
+            ctx.obs_shape = shape
+            return out.reshape(shape)
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            (grad,) = ctx.saved_tensors
+            g = grad_out.reshape(-1)
+            res = [None]
+            for d in range(grad.shape[0]):
+                res.append((g * grad[d]).reshape(ctx.obs_shape) if ctx.needs_input_grad[d + 1] else None)
+            return tuple(res)
+
+    _FUNCTION = _Interp
+    return _FUNCTION
+
+
+def interp(it, obs):
+    """Value of the multilinear interpolator `it` at `obs` (a sequence of N equally shaped torch CUDA tensors of the
+    handle's dtype), differentiable with respect to every tensor of `obs`."""
+    return _function().apply(it, *obs)

@@ -91,6 +91,28 @@ class _Base:
             raise TypeError(f"Unexpected data type: {dtype}")
         return self._interp().eval_lattice_host([np.ascontiguousarray(np.asarray(a).ravel()) for a in axes], out)
 
+    def eval_grad(self, obs, out=None, grad=None):
+        """Value and gradient at observation points (numpy arrays or torch CUDA tensors like `eval`): returns
+        `(out, grad)`, `out` with the bits of `eval` and `grad[d]` the derivative of the interpolant with respect to
+        coordinate d, shape `(N, *obs[0].shape)`.  Multilinear classes only: the others raise the library's
+        "unsupported" error (`InterpnHipError`)."""
+        obs = list(obs)
+        if obs and _is_tensor(obs[0]):
+            shape = tuple(obs[0].shape)
+            res, g = self._interp().eval_grad_tensors([o.reshape(-1).contiguous() for o in obs],
+                                                      None if out is None else out.reshape(-1),
+                                                      None if grad is None else grad.reshape(len(obs), -1))
+            self._interp().finish()
+            return res.reshape(shape), g.reshape((len(obs),) + shape)
+        dtype = self.vals.dtype
+        if dtype not in (np.float64, np.float32):
+            raise TypeError(f"Unexpected data type: {dtype}")
+        shape = np.asarray(obs[0]).shape if obs else (0,)
+        flat = [np.ascontiguousarray(np.asarray(o).ravel()) for o in obs]
+        res, g = self._interp().eval_grad_host(flat, None if out is None else out.reshape(-1),
+                                               None if grad is None else grad.reshape(len(obs), -1))
+        return res.reshape(shape), g.reshape((len(obs),) + tuple(shape))
+
     def eval_unchecked(self, obs, out=None):
         dtype = self.vals.dtype
         if dtype not in (np.float64, np.float32):

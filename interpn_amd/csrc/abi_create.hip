@@ -449,7 +449,7 @@ const char* interpn_hip_strerror(int status) {
     case INTERPN_HIP_ERR_UNREPRESENTABLE_NUMBER: return "Unrepresentable number";
     case INTERPN_HIP_ERR_REFERENCE_PANIC: return "the reference implementation panics on this input (slice length mismatch or integer overflow)";
     case INTERPN_HIP_ERR_INVALID_ARGUMENT: return "invalid argument";
-    case INTERPN_HIP_ERR_UNSUPPORTED: return "grid axis too long for the device kernels";
+    case INTERPN_HIP_ERR_UNSUPPORTED: return "unsupported: grid axis too long for the device kernels, or an operation this interpolator's method has no form of";
     case INTERPN_HIP_ERR_NO_DEVICE: return "no usable HIP device";
     case INTERPN_HIP_ERR_OUT_OF_MEMORY: return "out of device or pinned host memory";
     case INTERPN_HIP_ERR_HIP: return "HIP runtime error";

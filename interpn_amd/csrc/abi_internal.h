@@ -10,6 +10,7 @@
 //   abi_host.hip      host-pointer pipeline, small-batch path, finish, one-shot entry points
 //   abi_bounds.hip    check_bounds
 //   abi_sharded.hip   single-process multi-GPU forms
+//   abi_grad.hip      value and gradient of a multilinear handle (eval_grad_device / _host)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,13 @@
 
 #include "../../include/interpn_hip.h"
 #include "interpn_host.h"
+
+namespace interpn {
+// Multilinear value and gradient in one pass (k_linear_grad.hip, linear_grad.h): `grad` is a host array of ndims device
+// pointers.  The fused kernel for N = 2, 3 on the handle's re-laid table, the runtime-N kernel on `vals` otherwise.
+hipError_t launch_linear_grad(const GridDesc& g, const void* const* obs, void* out, void* const* grad, size_t npts,
+                              unsigned long long* first_bad, hipStream_t stream);
+}  // namespace interpn
 
 namespace interpn_abi {
 

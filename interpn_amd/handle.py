@@ -273,6 +273,82 @@ class Interpolator:
         self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
         return out
 
+    # -- value and gradient (multilinear handles) --------------------------------------------
+    def eval_grad_host(self, obs, out: np.ndarray = None, grad: np.ndarray = None):
+        """Value and gradient on host arrays (synchronous; `interpn_hip_eval_grad_host`): returns `(out, grad)` with
+        `out[i]` the bits of `eval_host` and `grad[d, i]` the derivative of the interpolant with respect to coordinate d
+        at point i (shape `(N, n)`), the slope of the cell the value path selects.  Multilinear handles only; on
+        "Unrepresentable coordinate value" exactly the entries in front of the failing point have been written."""
+        lib = _lib.load()
+        optr, olen, nobs, _keep = _slice_of_slices("obs", obs, self.dtype)
+        n = int(olen[0]) if nobs else 0
+        if out is None:
+            out = np.zeros(n, dtype=self.dtype)
+        if grad is None:
+            grad = np.zeros((nobs, n), dtype=self.dtype)
+        out = _check_arr("out", out, self.dtype, writable=True)
+        if not isinstance(grad, np.ndarray):
+            raise TypeError(f"argument 'grad': expected a numpy array, got {type(grad).__name__}")
+        if grad.dtype != self.dtype:
+            raise TypeError(f"argument 'grad': expected dtype {self.dtype.name}, got {grad.dtype.name}")
+        if grad.shape != (nobs, out.size):
+            raise ValueError(f"grad: expected shape {(nobs, out.size)}, got {grad.shape}")
+        if grad.size and grad.strides[-1] != grad.itemsize:
+            raise ValueError("argument 'grad': every row must be contiguous")
+        if not grad.flags.writeable:
+            raise ValueError("argument 'grad': array is read-only")
+        vp = (c_void_p * max(nobs, 1))()
+        gp = (c_void_p * max(nobs, 1))()
+        for i in range(nobs):
+            vp[i] = ctypes.cast(optr[i], c_void_p)
+            gp[i] = c_void_p(grad[i].ctypes.data)
+        st = lib.interpn_hip_eval_grad_host(self._h, vp, olen, nobs, out.ctypes.data_as(c_void_p), out.size, gp)
+        _lib.raise_for_status(st)
+        return out, grad
+
+    def eval_grad_tensors(self, obs, out=None, grad=None, stream=None):
+        """The same on torch CUDA tensors (`interpn_hip_eval_grad_device`): one kernel, asynchronous like `eval_tensors`
+        and capturable into a graph; `grad` is a tensor of shape `(N, n)` whose rows are contiguous.  `finish()`
+        synchronises and surfaces "Unrepresentable coordinate value"."""
+        import torch
+
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        obs = list(obs)
+        for i, t in enumerate(obs):
+            if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
+                raise TypeError(f"obs[{i}]: expected a contiguous 1-D {want} CUDA tensor")
+            self._check_same_device(f"obs[{i}]", t)
+        n = obs[0].numel() if obs else 0
+        for t in obs:
+            if t.numel() != n:
+                raise AssertionError("Dimension mismatch")
+        dev = torch.device("cuda", self.device())
+        if out is None:
+            out = torch.empty(n, dtype=want, device=dev)
+        elif not (out.is_cuda and out.is_contiguous() and out.dim() == 1 and out.dtype == want):
+            raise TypeError(f"out: expected a contiguous 1-D {want} CUDA tensor")
+        elif out.numel() != n:
+            raise AssertionError("Dimension mismatch")
+        else:
+            self._check_same_device("out", out)
+        if grad is None:
+            grad = torch.empty((len(obs), n), dtype=want, device=dev)
+        elif not (grad.is_cuda and grad.dim() == 2 and grad.dtype == want and (grad.numel() == 0 or grad.stride(1) == 1)):
+            raise TypeError(f"grad: expected a 2-D {want} CUDA tensor with contiguous rows")
+        elif tuple(grad.shape) != (len(obs), n):
+            raise ValueError(f"grad: expected shape {(len(obs), n)}, got {tuple(grad.shape)}")
+        else:
+            self._check_same_device("grad", grad)
+        owner = torch.cuda.current_stream(self.device()) if stream is None else stream
+        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        k = len(obs)
+        vp = (c_void_p * max(k, 1))(*[t.data_ptr() for t in obs])
+        gp = (c_void_p * max(k, 1))(*[grad[d].data_ptr() for d in range(k)])
+        st = _lib.load().interpn_hip_eval_grad_device(self._h, vp, k, c_void_p(out.data_ptr()), gp, n, c_void_p(int(raw)))
+        _lib.raise_for_status(st)
+        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        return out, grad
+
     # -- lattice evaluation (points = tensor product of one coordinate vector per axis) ----
     @property
     def last_lattice_path(self):
