@@ -617,6 +617,53 @@ int interpn_hip_reserve_lattice(interpn_hip_interp* h, const size_t* axis_lens, 
 int interpn_hip_lattice_plan(size_t elem_size, int method, size_t ndims, const size_t* dims, const size_t* axis_lens,
                              int* path, size_t* lds_bytes, size_t* npoints);
 
+/* ------------------------------------------------------------------------------------------
+ * Point-major observation points — the points as ONE array of shape (npoints, N), the layout of particle positions, ray
+ * samples and scipy's `xi`, instead of N coordinate arrays.
+ *
+ * Definition  a block is a pointer `pts`, a count `npoints` and a `point_stride` >= ndims in ELEMENTS: coordinate d of
+ *           point i is pts[i * point_stride + d].  point_stride > ndims covers buf[:, :3] of an (n, 4) array and records
+ *           that carry other fields; elements d >= ndims of a row are never read.
+ * Contract  the result of point i has exactly the bits of interpn_hip_eval_device on the N de-interleaved coordinate
+ *           arrays, for every method, kind, N = 1..8, element type and fma flavour.  A failing point ("Unrepresentable
+ *           coordinate value", regular grids) is reported as by interpn_hip_eval_device / _host, with the index of the
+ *           point in the whole call.
+ * Paths     FUSED (multilinear N = 2, 3 on a handle with a re-laid table): interpn::k_linear_points reads the rows
+ *           directly — packed rows (point_stride == N) whose base is aligned to two elements as per-lane vector loads of
+ *           the lane's own PPL * N consecutive elements (3-D f64: the wave's whole span through LDS, which measured
+ *           faster), anything else element by element — and is otherwise the value
+ *           kernel: one launch, no scratch, no allocation, capturable.
+ *           DIRECT (N = 1 with point_stride == 1): the block is a coordinate array; interpn_hip_eval_device_ex, no copy.
+ *           SPLIT (everything else: cubic, nearest, one_dim with a stride, N >= 4, handles without a table, option
+ *           force_generic): interpn::k_split_points de-interleaves a slice (64 MiB of coordinates at most) into scratch and
+ *           the slice goes through interpn_hip_eval_device_ex with all its paths and options.
+ * Options   "points_path" = 0 automatic (fused where it exists), 1 fused or INTERPN_HIP_ERR_UNSUPPORTED, 2 split.
+ *           "points_load" = 0 automatic (3-D f64: 2; else 1), 1 per-lane vector loads, 2 (3-D f64) the span through LDS, 3 element loads.
+ *           "points_slice" (testing): points per slice of the split path.  Read-only "last_points_path"
+ *           (INTERPN_HIP_POINTS_PATH_*; -1 before any).  interpn_hip_kernel_name reports "interpn::k_linear_points<...>"
+ *           after a fused evaluation, the ordinary kernel otherwise.
+ * Scratch   the split path works in one of the handle's scratch blocks under the rules of the lattice's expanded path:
+ *           one block per concurrent stream, at most 4, allocated on first use unless INTERPN_HIP_EVAL_NO_ALLOC is given
+ *           (then INTERPN_HIP_ERR_OUT_OF_MEMORY without one); interpn_hip_reserve_points provides them in advance; a
+ *           stream under graph capture uses reserved blocks only.
+ * Checks    before any device work, in this order: h NULL, point_stride < ndims (one_dim handles: < 1):
+ *           INTERPN_HIP_ERR_INVALID_ARGUMENT; npoints == 0: INTERPN_HIP_OK whatever the other pointers are; pts or out
+ *           NULL: INTERPN_HIP_ERR_INVALID_ARGUMENT; option points_path = 1 without a fused kernel:
+ *           INTERPN_HIP_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------- */
+enum { INTERPN_HIP_POINTS_PATH_FUSED = 0, INTERPN_HIP_POINTS_PATH_SPLIT = 1, INTERPN_HIP_POINTS_PATH_DIRECT = 2 };
+/* Asynchronous on `stream`.  `pts`, `out` (npoints elements): device.  `flags`: INTERPN_HIP_EVAL_NO_ALLOC.  *path_taken
+ * (may be NULL): INTERPN_HIP_POINTS_PATH_*.  interpn_hip_finish reports a failing point. */
+int interpn_hip_eval_points_device(interpn_hip_interp* h, const void* pts, size_t point_stride, size_t npoints, void* out,
+                                   void* stream, unsigned flags, int* path_taken);
+/* The same on host arrays, synchronous: chunks of 2^21 points (option "host_chunk"), the interleaved rows of a chunk
+ * uploaded with one copy.  On a failing point the status is the handle's, exactly out[0..first_bad) is written and the rest
+ * of `out` is left as it was.  Shares the sticky status word with the device form: finish device evaluations first. */
+int interpn_hip_eval_points_host(interpn_hip_interp* h, const void* pts, size_t point_stride, size_t npoints, void* out);
+/* Scratch blocks for split-path evaluations of up to `npoints` points on up to `nstreams` concurrent streams.
+ * Synchronous.  (A slice that the handle would sort or sweep takes a second block: interpn_hip_reserve.) */
+int interpn_hip_reserve_points(interpn_hip_interp* h, size_t npoints, int nstreams);
+
 #ifdef __cplusplus
 }
 #endif

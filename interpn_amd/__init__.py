@@ -42,6 +42,7 @@ __all__ = [
     "interpn_fields",
     "interpn_grad",
     "interpn_lattice",
+    "interpn_points",
     "lattice_plan",
     "Fields",
     "fields_layout",
@@ -243,6 +244,93 @@ def interpn_grad(
     finally:
         it.close()
     return out.reshape(shape), grad.reshape((len(flat),) + shape)
+
+
+def interpn_points(
+    xi,
+    grids: Sequence,
+    vals,
+    *,
+    method: Literal["linear", "cubic", "nearest"] = "linear",
+    out=None,
+    linearize_extrapolation: bool = True,
+    assume_regular: bool = False,
+    check_bounds: bool = False,
+    bounds_atol: float = 1e-8,
+):
+    """`interpn()` for points kept as ONE array `xi` of shape `(..., N)` — scipy's `xi`, particle positions, ray samples:
+    returns an array (numpy `xi`) or a tensor (torch CUDA `xi`) of shape `xi.shape[:-1]` whose entries have the bits of
+    `interpn([xi[..., 0], .., xi[..., N-1]], grids, vals, ...)`.  The columns are never made: multilinear N = 2, 3 reads
+    the rows in its one kernel, everything else de-interleaves slices of them on the device.
+
+    The rules are those of `interpn()`: dtype from `vals` (`xi` must have it), regular iff every spacing is exactly equal
+    or `assume_regular`.  `check_bounds` unstacks the columns for the existing check."""
+    if method not in ("linear", "cubic", "nearest"):
+        raise ValueError(f"Unsupported interpolation configuration: {method}")
+    on_device = _is_cuda_tensor(xi)
+    if not on_device:
+        xi = np.asarray(xi)
+    if len(xi.shape) < 1 or xi.shape[-1] != len(grids):
+        raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+    if not (_is_cuda_tensor(vals) or isinstance(vals, np.ndarray)):
+        raise TypeError("argument 'vals': expected a numpy array or a torch tensor")
+    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
+    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
+    vals = vals.reshape(-1).contiguous() if _is_cuda_tensor(vals) else np.ascontiguousarray(vals.ravel())
+    grids = [np.ascontiguousarray(np.asarray(x).ravel()).astype(dtype, copy=False) for x in grids]
+    shape = tuple(xi.shape[:-1])
+    n = len(grids)
+    device = -1
+    if on_device:
+        import torch
+
+        device = xi.device.index if xi.device.index is not None else torch.cuda.current_device()
+        flat = xi if xi.dim() == 2 else xi.reshape(-1, n)
+        if n > 1 and flat.stride(1) != 1:
+            flat = flat.contiguous()
+    else:
+        flat = xi if xi.ndim == 2 else xi.reshape(-1, n)
+        if n > 1 and flat.strides[1] != flat.itemsize:
+            flat = np.ascontiguousarray(flat)
+    is_regular = assume_regular or _check_regular(grids)
+    if is_regular:
+        dims = [len(g) for g in grids]
+        starts = np.array([g[0] for g in grids], dtype=dtype)
+        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
+        it = Interpolator.regular(method, dims, starts, steps, vals, linearize_extrapolation=linearize_extrapolation,
+                                  device=device, dtype=dtype)
+    else:
+        it = Interpolator.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation, device=device,
+                                      dtype=dtype)
+    try:
+        if check_bounds:
+            if on_device:
+                violated = it.check_bounds_tensors([flat[:, d].contiguous() for d in range(n)], bounds_atol).any()
+            else:
+                sfx = "f64" if dtype == np.float64 else "f32"
+                cols = [np.ascontiguousarray(flat[:, d]) for d in range(n)]
+                outb = np.zeros(n, dtype=bool)
+                if is_regular:
+                    getattr(raw, f"check_bounds_regular_{sfx}")(dims, starts, steps, cols, bounds_atol, outb)
+                else:
+                    getattr(raw, f"check_bounds_rectilinear_{sfx}")(grids, cols, bounds_atol, outb)
+                violated = any(outb)
+            if violated:
+                raise ValueError("Observation points violate interpolator bounds")
+        if out is not None:
+            if on_device and not out.is_contiguous():
+                raise ValueError("out: expected a contiguous CUDA tensor")
+            if not on_device and not (isinstance(out, np.ndarray) and out.flags.c_contiguous):
+                raise ValueError("argument 'out': The given array is not contiguous")
+            out = out.reshape(-1)
+        if on_device:
+            res = it.eval_points_tensors(flat, out)
+            it.finish()
+        else:
+            res = it.eval_points_host(flat, out)
+    finally:
+        it.close()
+    return res.reshape(shape)
 
 
 def interpn_lattice(

@@ -36,6 +36,7 @@ PATH_IN_PLACE, PATH_BINNED, PATH_SWEEP = 0, 1, 2
 FIELDS_PATH_FUSED, FIELDS_PATH_PER_FIELD = 0, 1  # interpn_hip_fields_eval_device
 LATTICE_PATH_FUSED, LATTICE_PATH_EXPANDED = 0, 1  # interpn_hip_eval_lattice_device
 LATTICE_PATHS = {LATTICE_PATH_FUSED: "fused", LATTICE_PATH_EXPANDED: "expanded"}
+POINTS_PATHS = {0: "fused", 1: "split", 2: "direct"}  # interpn_hip_eval_points_device
 EVAL_NO_ALLOC = 1
 WHY = {0: "", 1: "batch below the break-even size or option binned = 0", 2: "stream under graph capture",
        3: "no reserved scratch block free and allocation not allowed", 4: "scratch allocation failed",
@@ -185,6 +186,10 @@ def load() -> ctypes.CDLL:
     lib.interpn_hip_reserve_lattice.argtypes = [c_void_p, POINTER(c_size_t), c_size_t, c_int]
     lib.interpn_hip_lattice_plan.argtypes = [c_size_t, c_int, c_size_t, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_int),
                                              POINTER(c_size_t), POINTER(c_size_t)]
+    lib.interpn_hip_eval_points_device.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, ctypes.c_uint,
+                                                   POINTER(c_int)]
+    lib.interpn_hip_eval_points_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
+    lib.interpn_hip_reserve_points.argtypes = [c_void_p, c_size_t, c_int]
     _lib = lib
     return lib
 

@@ -113,6 +113,26 @@ class _Base:
                                                None if grad is None else grad.reshape(len(obs), -1))
         return res.reshape(shape), g.reshape((len(obs),) + tuple(shape))
 
+    def eval_points(self, pts, out=None):
+        """Evaluate at points given as ONE array of shape `(..., N)` (numpy, or a torch CUDA tensor like `eval`): the
+        result has shape `pts.shape[:-1]` and the bits of `eval` on the N unstacked columns, which are never made."""
+        shape = tuple(pts.shape[:-1])
+        if _is_tensor(pts):
+            flat = pts if pts.dim() == 2 else pts.reshape(-1, pts.shape[-1])
+            if flat.shape[1] > 1 and flat.stride(1) != 1:
+                flat = flat.contiguous()
+            res = self._interp().eval_points_tensors(flat, None if out is None else out.reshape(-1))
+            self._interp().finish()
+            return res.reshape(shape)
+        dtype = self.vals.dtype
+        if dtype not in (np.float64, np.float32):
+            raise TypeError(f"Unexpected data type: {dtype}")
+        pts = np.asarray(pts)
+        flat = pts if pts.ndim == 2 else pts.reshape(-1, pts.shape[-1])
+        if flat.shape[1] > 1 and flat.strides[1] != flat.itemsize:
+            flat = np.ascontiguousarray(flat)
+        return self._interp().eval_points_host(flat, None if out is None else out.reshape(-1)).reshape(shape)
+
     def eval_unchecked(self, obs, out=None):
         dtype = self.vals.dtype
         if dtype not in (np.float64, np.float32):

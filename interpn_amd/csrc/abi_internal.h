@@ -11,6 +11,7 @@
 //   abi_bounds.hip    check_bounds
 //   abi_sharded.hip   single-process multi-GPU forms
 //   abi_grad.hip      value and gradient of a multilinear handle (eval_grad_device / _host)
+//   abi_points.hip    point-major observation points (eval_points_device / _host, reserve_points)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,6 +39,16 @@ namespace interpn {
 // pointers.  The fused kernel for N = 2, 3 on the handle's re-laid table, the runtime-N kernel on `vals` otherwise.
 hipError_t launch_linear_grad(const GridDesc& g, const void* const* obs, void* out, void* const* grad, size_t npts,
                               unsigned long long* first_bad, hipStream_t stream);
+// Point-major observation points (k_linear_points.hip, linear_points.h): coordinate d of point i at pts[i * stride + d].
+// The fused kernel (N = 2, 3 multilinear on the handle's re-laid table); the de-interleaving of a slice into ndims
+// coordinate arrays (`dst`: host array of device pointers); and the two one-lane kernels around a slice that starts at
+// point `begin` of its call, which keep the first-failing-index word counting from the call's first point.
+bool points_fused_applies(const GridDesc& g);
+hipError_t launch_linear_points(const GridDesc& g, const void* pts, size_t stride, void* out, size_t npts,
+                                unsigned long long* first_bad, hipStream_t stream);
+hipError_t launch_split_points(const GridDesc& g, const void* pts, size_t stride, void* const* dst, size_t count, hipStream_t stream);
+hipError_t launch_points_bad_begin(unsigned long long* word, unsigned long long* saved, hipStream_t stream);
+hipError_t launch_points_bad_end(unsigned long long* word, const unsigned long long* saved, unsigned long long begin, hipStream_t stream);
 }  // namespace interpn
 
 namespace interpn_abi {
@@ -302,6 +313,17 @@ hipError_t wait_status_word(hipStream_t s, const unsigned long long* word);
 int binned_applies(const GridDesc& g, size_t npoints);
 interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, hipStream_t stream, bool may_alloc, int* why);
 void release_bin_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot, hipStream_t stream, bool staged);
+
+// abi_lattice.hip: scratch blocks of the paths that fill one themselves and hand it to interpn_hip_eval_device_ex (the
+// lattice's expanded path, the point-major split path).  Under graph capture a block is taken without touching any event;
+// claim_slot drops what the sort and the sweep remembered about the block's contents; reserve_slots makes sure
+// `nstreams` blocks of at least `need` bytes exist (the current device is the handle's).
+interpn_hip_interp::BinSlot* take_slot_captured(interpn_hip_interp* h, size_t need, hipStream_t stream);
+void release_slot_captured(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot);
+void claim_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot);
+int reserve_slots(interpn_hip_interp* h, size_t need, int nstreams);
+constexpr size_t kExpandSliceBytes = (size_t)64 << 20;  // coordinates of one slice (bounds the scratch block)
+constexpr size_t kExpandSliceMin = (size_t)1 << 16;     // ... but never fewer points than this
 
 // abi_sweep.hip
 int eval_device_sweep(interpn_hip_interp* h, const void* const* obs, void* out, size_t npoints, hipStream_t stream,

@@ -6,10 +6,80 @@
 using namespace interpn;
 using namespace interpn_abi;
 
+namespace interpn_abi {
+
+using Slot = interpn_hip_interp::BinSlot;
+
+// Under graph capture no event of a block may be queried, waited for or recorded (the captured launch may replay at any
+// later time): take a block that is large enough without any of that.  The caller keeps other streams away from the
+// handle while such a graph replays (include/interpn_hip.h).
+Slot* take_slot_captured(interpn_hip_interp* h, size_t need, hipStream_t stream) {
+  std::lock_guard<std::mutex> lk(h->bin_mu);
+  Slot* pick = nullptr;
+  for (auto& sl : h->bin_slots) {
+    if (sl.busy || sl.bytes < need) continue;
+    if (!pick || sl.last_stream == stream) pick = &sl;
+  }
+  if (pick) {
+    pick->busy = true;
+    pick->stamp = ++h->bin_uses;
+  }
+  return pick;
+}
+
+void release_slot_captured(interpn_hip_interp* h, Slot* slot) {
+  std::lock_guard<std::mutex> lk(h->bin_mu);
+  slot->busy = false;
+}
+
+// The block's contents are the caller's now: the sort's and the sweep's invariants about it are gone.
+void claim_slot(interpn_hip_interp* h, Slot* slot) {
+  std::lock_guard<std::mutex> lk(h->bin_mu);
+  slot->totals_clean = false;
+  slot->sweep_clean = false;
+  slot->staged = false;
+  const unsigned char* word = static_cast<const unsigned char*>(h->sampling.last_word);
+  const unsigned char* base = static_cast<const unsigned char*>(slot->scratch);
+  if (word && word >= base && word < base + slot->bytes) h->sampling.last_word = nullptr;
+}
+
+int reserve_slots(interpn_hip_interp* h, size_t need, int nstreams) {
+  std::lock_guard<std::mutex> lk(h->bin_mu);
+  int have = 0;
+  for (auto& sl : h->bin_slots)
+    if (sl.bytes >= need) ++have;
+  for (auto& sl : h->bin_slots) {  // grow idle blocks that are too small first, then add new ones (as interpn_hip_reserve)
+    if (have >= nstreams) break;
+    if (sl.bytes >= need || sl.busy) continue;
+    if (sl.recorded) HIP_TRY(hipEventSynchronize(sl.event));
+    pool_free(h->device, sl.scratch);
+    h->sampling.last_word = nullptr;
+    sl.scratch = nullptr;
+    sl.bytes = 0;
+    sl.totals_clean = false;
+    sl.sweep_clean = false;
+    sl.recorded = false;
+    if (pool_alloc(h->device, &sl.scratch, need) != hipSuccess) { (void)hipGetLastError(); sl.scratch = nullptr; return INTERPN_HIP_ERR_OUT_OF_MEMORY; }
+    sl.bytes = need;
+    h->scratch_allocs.fetch_add(1);
+    ++have;
+  }
+  while (have < nstreams && h->bin_slots.size() < interpn_hip_interp::kMaxBinSlots) {
+    Slot sl;
+    HIP_TRY(hipEventCreateWithFlags(&sl.event, hipEventDisableTiming));
+    if (pool_alloc(h->device, &sl.scratch, need) != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(sl.event); return INTERPN_HIP_ERR_OUT_OF_MEMORY; }
+    sl.bytes = need;
+    h->scratch_allocs.fetch_add(1);
+    h->bin_slots.push_back(sl);
+    ++have;
+  }
+  return have >= nstreams ? INTERPN_HIP_OK : INTERPN_HIP_ERR_OUT_OF_MEMORY;
+}
+
+}  // namespace interpn_abi
+
 namespace {
 
-constexpr size_t kExpandSliceBytes = (size_t)64 << 20;  // expanded path: coordinates of one slice (bounds the scratch block)
-constexpr size_t kExpandSliceMin = (size_t)1 << 16;     // ... but never fewer points than this
 constexpr size_t kHostChunkPointsLattice = (size_t)1 << 25;  // host form: lattice points per chunk of leading-axis indices
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -58,41 +128,6 @@ size_t scratch_need(const GridDesc& g, const LatticeShape& s, const LatticePlan&
   if (p.fused) return align_up(s.coords * lattice_record_bytes(g.method, g.kind, elem), 256);
   const size_t flags = g.kind == kRegular ? align_up(s.coords, 256) : 0;
   return flags + (size_t)g.ndims * align_up(expand_slice(g, s.npoints) * elem, 256);
-}
-
-using Slot = interpn_hip_interp::BinSlot;
-
-// Under graph capture no event of a block may be queried, waited for or recorded (the captured launch may replay at any
-// later time): take a block that is large enough without any of that.  The caller keeps other streams away from the
-// handle while such a graph replays (include/interpn_hip.h).
-Slot* take_slot_captured(interpn_hip_interp* h, size_t need, hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(h->bin_mu);
-  Slot* pick = nullptr;
-  for (auto& sl : h->bin_slots) {
-    if (sl.busy || sl.bytes < need) continue;
-    if (!pick || sl.last_stream == stream) pick = &sl;
-  }
-  if (pick) {
-    pick->busy = true;
-    pick->stamp = ++h->bin_uses;
-  }
-  return pick;
-}
-
-void release_slot_captured(interpn_hip_interp* h, Slot* slot) {
-  std::lock_guard<std::mutex> lk(h->bin_mu);
-  slot->busy = false;
-}
-
-// The block's contents are the lattice's now: the sort's and the sweep's invariants about it are gone.
-void claim_slot(interpn_hip_interp* h, Slot* slot) {
-  std::lock_guard<std::mutex> lk(h->bin_mu);
-  slot->totals_clean = false;
-  slot->sweep_clean = false;
-  slot->staged = false;
-  const unsigned char* word = static_cast<const unsigned char*>(h->sampling.last_word);
-  const unsigned char* base = static_cast<const unsigned char*>(slot->scratch);
-  if (word && word >= base && word < base + slot->bytes) h->sampling.last_word = nullptr;
 }
 
 // One lattice on device arrays.  Arguments are validated; the current device is the handle's.
@@ -235,36 +270,7 @@ int interpn_hip_reserve_lattice(interpn_hip_interp* h, const size_t* axis_lens, 
   }
   DeviceGuard guard(h->device);
   if (!guard.ok()) return INTERPN_HIP_ERR_NO_DEVICE;
-  std::lock_guard<std::mutex> lk(h->bin_mu);
-  int have = 0;
-  for (auto& sl : h->bin_slots)
-    if (sl.bytes >= need) ++have;
-  for (auto& sl : h->bin_slots) {  // grow idle blocks that are too small first, then add new ones (as interpn_hip_reserve)
-    if (have >= nstreams) break;
-    if (sl.bytes >= need || sl.busy) continue;
-    if (sl.recorded) HIP_TRY(hipEventSynchronize(sl.event));
-    pool_free(h->device, sl.scratch);
-    h->sampling.last_word = nullptr;
-    sl.scratch = nullptr;
-    sl.bytes = 0;
-    sl.totals_clean = false;
-    sl.sweep_clean = false;
-    sl.recorded = false;
-    if (pool_alloc(h->device, &sl.scratch, need) != hipSuccess) { (void)hipGetLastError(); sl.scratch = nullptr; return INTERPN_HIP_ERR_OUT_OF_MEMORY; }
-    sl.bytes = need;
-    h->scratch_allocs.fetch_add(1);
-    ++have;
-  }
-  while (have < nstreams && h->bin_slots.size() < interpn_hip_interp::kMaxBinSlots) {
-    Slot sl;
-    HIP_TRY(hipEventCreateWithFlags(&sl.event, hipEventDisableTiming));
-    if (pool_alloc(h->device, &sl.scratch, need) != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(sl.event); return INTERPN_HIP_ERR_OUT_OF_MEMORY; }
-    sl.bytes = need;
-    h->scratch_allocs.fetch_add(1);
-    h->bin_slots.push_back(sl);
-    ++have;
-  }
-  return have >= nstreams ? INTERPN_HIP_OK : INTERPN_HIP_ERR_OUT_OF_MEMORY;
+  return reserve_slots(h, need, nstreams);
 }
 
 int interpn_hip_eval_lattice_host(interpn_hip_interp* h, const void* const* axes, const size_t* axis_lens, size_t naxes,

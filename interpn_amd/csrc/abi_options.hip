@@ -45,6 +45,8 @@ bool option_access(LaunchConfig& c, const char* name, long long* value, bool set
       {"gated_iters", &c.gated_iters, 0, 4096},
       {"finish_kernel", &c.finish_kernel, 0, 1},
       {"lattice", &c.lattice, -1, 1},
+      {"points_path", &c.points_path, 0, 2},
+      {"points_load", &c.points_load, 0, 3},
   };
   if (!name || !value) return false;
   if (!strcmp(name, "host_chunk")) {
@@ -53,6 +55,15 @@ bool option_access(LaunchConfig& c, const char* name, long long* value, bool set
       c.host_chunk = *value;
     } else {
       *value = c.host_chunk;
+    }
+    return true;
+  }
+  if (!strcmp(name, "points_slice")) {
+    if (set) {
+      if (*value < 0) return false;
+      c.points_slice = *value;
+    } else {
+      *value = c.points_slice;
     }
     return true;
   }
@@ -87,7 +98,7 @@ bool option_access(LaunchConfig& c, const char* name, long long* value, bool set
 void latch_env(LaunchConfig& c) {
   static const char* const names[] = {"blocks_per_cu", "iters_per_block", "ppl", "axis_regs", "force_generic",
                                       "generic_runtime", "generic_vec", "persistent", "axis_lds_kb", "host_chunk", "binned", "deal",
-                                      "bin_slice_log2", "column", "column_part", "column_threads", "column_groups", "column_cpp", "column_coef", "column_pad", "hist_wgs_per_cu", "column_keys", "column_tail", "scatter_staged", "axis_records", "bin_scramble", "sweep", "sweep_period", "sweep_probe", "gated_iters", "finish_kernel", "lattice"};
+                                      "bin_slice_log2", "column", "column_part", "column_threads", "column_groups", "column_cpp", "column_coef", "column_pad", "hist_wgs_per_cu", "column_keys", "column_tail", "scatter_staged", "axis_records", "bin_scramble", "sweep", "sweep_period", "sweep_probe", "gated_iters", "finish_kernel", "lattice", "points_path", "points_load", "points_slice"};
   for (const char* nm : names) {
     char var[64] = "INTERPN_HIP_";
     size_t k = strlen(var);
@@ -130,6 +141,7 @@ int interpn_hip_get_option(const interpn_hip_interp* h, const char* name, long l
   }
   if (!strcmp(name, "fma")) { *value = h->desc.fma; return INTERPN_HIP_OK; }
   if (!strcmp(name, "last_lattice_path")) { *value = h->desc.last_lattice_path; return INTERPN_HIP_OK; }  // read-only: INTERPN_HIP_LATTICE_PATH_*, -1 before any lattice evaluation
+  if (!strcmp(name, "last_points_path")) { *value = h->desc.last_points_path; return INTERPN_HIP_OK; }  // read-only: INTERPN_HIP_POINTS_PATH_*, -1 before any point-major evaluation
   // read-only: how the handle's rectilinear axes will be searched (0 no records, 1 full, 2 compact) and what is staged
   if (!strcmp(name, "axis_rec_mode")) { *value = h->desc.axis_rec_bytes ? (h->desc.axis_rec_compact ? 2 : 1) : 0; return INTERPN_HIP_OK; }
   if (!strcmp(name, "axis_rec_bytes")) { *value = h->desc.axis_rec_bytes; return INTERPN_HIP_OK; }

@@ -61,6 +61,9 @@ struct LaunchConfig {
   int sweep_probe = 2;     // automatic sweep launches: sample the batch on the device first and let the one-pass kernel take coherent batches — 0: never (the sweep kernel whatever the points look like), 1: every launch, 2: every launch until three samples in a row came out unordered, then every 16th (abi_sweep.hip)
   // (sweep itself: -1 automatic, 0 never, 1 always, 2 always with the sample deciding between the two kernels)
   int lattice = -1;        // lattice evaluation (lattice.h): -1 the row kernel where the layout rules of lattice_plan say it pays, 0 never (expand and evaluate), 1 wherever it is covered and its lines fit the LDS budget
+  int points_path = 0;     // point-major evaluation (linear_points.h): 0 automatic, 1 the fused kernel or INTERPN_HIP_ERR_UNSUPPORTED, 2 de-interleave and evaluate
+  int points_load = 0;     // the fused kernel's coordinate load on packed, aligned rows: 0 automatic (3-D f64: 2, else 1), 1 per-lane vector loads, 2 the wave's span through LDS (3-D f64), 3 element loads
+  long long points_slice = 0;  // testing: points per slice of the split path (0 = 64 MiB of coordinates; rounded down to a multiple of 256)
   int sweep_period = 0;    // sweep evaluation: ticks of 10 ns per sweep of the leading index (0: what the previous launch measured; 1: no clock, rows in sorted order; tests / tuning)
 };
 
@@ -181,6 +184,7 @@ struct GridDesc {
   LaunchConfig cfg;
   mutable KernelTag tag;
   mutable int last_lattice_path = -1;  // the most recent lattice evaluation: INTERPN_HIP_LATTICE_PATH_*, -1 before any
+  mutable int last_points_path = -1;   // the most recent point-major evaluation: INTERPN_HIP_POINTS_PATH_*, -1 before any
   mutable int last_binned = 0;  // the most recent device-pointer evaluation sorted its points first (binned evaluation)
 };
 

@@ -349,6 +349,87 @@ class Interpolator:
         self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
         return out, grad
 
+    # -- point-major observation points (one array of shape (n, N)) ---------------------------
+    def last_points_path(self):
+        """"fused", "split" or "direct": what the most recent point-major evaluation did (None before any)."""
+        return _lib.POINTS_PATHS.get(self.get_option("last_points_path"))
+
+    def reserve_points(self, npoints: int, nstreams: int = 1) -> None:
+        """Pre-allocate the scratch that point-major evaluations of up to `npoints` points on up to `nstreams` concurrent
+        streams need where they de-interleave the points first (`interpn_hip_reserve_points`); afterwards they work with
+        `no_alloc=True`.  The fused kernel (multilinear N = 2, 3) needs none."""
+        _lib.raise_for_status(_lib.load().interpn_hip_reserve_points(self._h, int(npoints), int(nstreams)))
+
+    def eval_points_host(self, pts: np.ndarray, out: np.ndarray = None) -> np.ndarray:
+        """`.interp` on a host array of shape `(n, N)` whose rows are points (synchronous; `interpn_hip_eval_points_host`):
+        `out[i]` has the bits of `eval_host` on the columns `pts[:, d]`, which are never made.  Rows must be contiguous
+        (`pts.strides[1] == itemsize`); the row stride may be any whole number of elements >= N, so `buf[:, :3]` of an
+        `(n, 4)` array is taken as it is.  On "Unrepresentable coordinate value" exactly the results in front of the
+        failing point have been written."""
+        if not isinstance(pts, np.ndarray):
+            raise TypeError(f"argument 'pts': expected a numpy array, got {type(pts).__name__}")
+        if pts.dtype != self.dtype:
+            raise TypeError(f"argument 'pts': expected dtype {self.dtype.name}, got {pts.dtype.name}")
+        if pts.ndim != 2:
+            raise TypeError(f"argument 'pts': expected a 2-D array of shape (n, {self._ndims}), got {pts.ndim} dimension(s)")
+        n, width = pts.shape
+        if width != self._ndims:
+            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        item = pts.itemsize
+        stride = self._ndims
+        if n > 1 or width > 1:
+            if width > 1 and pts.strides[1] != item:
+                raise ValueError("argument 'pts': every row must be contiguous")
+            if n > 1:
+                if pts.strides[0] % item or pts.strides[0] < self._ndims * item:
+                    raise ValueError(f"argument 'pts': the row stride must be a whole number of elements, at least {self._ndims}")
+                stride = pts.strides[0] // item
+        if out is None:
+            out = np.zeros(n, dtype=self.dtype)
+        out = _check_arr("out", out, self.dtype, writable=True)
+        if out.size != n:
+            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        st = _lib.load().interpn_hip_eval_points_host(self._h, c_void_p(pts.ctypes.data), stride, n, out.ctypes.data_as(c_void_p))
+        _lib.raise_for_status(st)
+        return out
+
+    def eval_points_tensors(self, pts, out=None, stream=None, no_alloc: bool = False):
+        """The same on a torch CUDA tensor of shape `(n, N)` with `stride(1) == 1` and `stride(0) >= N` — a contiguous
+        `(n, N)` tensor, or `buf[:, :N]` of a wider one — without `pts.T.contiguous()` (`interpn_hip_eval_points_device`).
+        Asynchronous like `eval_tensors`; multilinear N = 2, 3 is one kernel and capturable.  `last_points_path()` says
+        which path ran; `finish()` synchronises and surfaces "Unrepresentable coordinate value"."""
+        import torch
+
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        nd = self._ndims
+        what = f"pts: expected a 2-D {want} CUDA tensor of shape (n, {nd}) with stride(1) == 1 and stride(0) >= {nd}"
+        if not (hasattr(pts, "is_cuda") and pts.is_cuda and pts.dim() == 2 and pts.dtype == want):
+            raise TypeError(what)
+        n, width = int(pts.shape[0]), int(pts.shape[1])
+        if (width > 1 and pts.stride(1) != 1) or (n > 1 and pts.stride(0) < width):
+            raise TypeError(what)
+        if width != nd:
+            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        self._check_same_device("pts", pts)
+        stride = int(pts.stride(0)) if n > 1 else nd
+        if out is None:
+            out = torch.empty(n, dtype=want, device=torch.device("cuda", self.device()))
+        elif not (out.is_cuda and out.is_contiguous() and out.dim() == 1 and out.dtype == want):
+            raise TypeError(f"out: expected a contiguous 1-D {want} CUDA tensor")
+        elif out.numel() != n:
+            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        else:
+            self._check_same_device("out", out)
+        owner = torch.cuda.current_stream(self.device()) if stream is None else stream
+        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        path = ctypes.c_int(0)
+        st = _lib.load().interpn_hip_eval_points_device(self._h, c_void_p(pts.data_ptr()), stride, n, c_void_p(out.data_ptr()),
+                                                        c_void_p(int(raw)), _lib.EVAL_NO_ALLOC if no_alloc else 0,
+                                                        ctypes.byref(path))
+        _lib.raise_for_status(st)
+        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        return out
+
     # -- lattice evaluation (points = tensor product of one coordinate vector per axis) ----
     @property
     def last_lattice_path(self):
