@@ -123,7 +123,8 @@ typedef enum interpn_hip_status {
   /* statuses of this implementation */
   INTERPN_HIP_ERR_INVALID_ARGUMENT = 32, /* null pointer, unknown enum value, dtype mismatch */
   INTERPN_HIP_ERR_UNSUPPORTED = 33,      /* axis longer than 2^31-257 points (f32: 2^24); interpn_hip_eval_grad_* on a handle
-                                            that is not multilinear (multicubic, nearest, interpn::one_dim) */
+                                            that is not multilinear (multicubic, nearest, interpn::one_dim);
+                                            interpn_hip_eval_cubic_grad_* on a handle that is not multicubic */
   INTERPN_HIP_ERR_NO_DEVICE = 34,        /* no usable HIP device */
   INTERPN_HIP_ERR_OUT_OF_MEMORY = 35,    /* device or pinned-host allocation failed */
   INTERPN_HIP_ERR_HIP = 36               /* any other HIP runtime failure (see interpn_hip_last_hip_error) */
@@ -356,6 +357,38 @@ int interpn_hip_eval_grad_device(interpn_hip_interp* h, const void* const* obs, 
                                  void* const* grad, size_t npoints, void* stream);
 int interpn_hip_eval_grad_host(interpn_hip_interp* h, const void* const* obs, const size_t* obs_lens, size_t nobs,
                                void* out, size_t nout, void* const* grad);
+
+/* ------------------------------------------------------------------------------------------
+ * Value and gradient of a MULTICUBIC handle: out[i] = f(x_i) with the bits of interpn_hip_eval_*, and
+ * grad[d][i] = df/dx_d at x_i, the derivative of the C1 Hermite interpolant, from the 4^N table values the value is made
+ * of (one pass over the points, no table read beyond a value call's).  Entry points of their own: the multilinear pair
+ * above keeps returning INTERPN_HIP_ERR_UNSUPPORTED on a multicubic handle.
+ * The reference has no gradient; the definition (DESIGN.md "Multicubic gradients") is, per point, at the handle's fma
+ * flavour and on the arm of the reference the value path runs (flattened for N <= 4, recursive for N >= 5): per dimension
+ * e the value path's footprint origin, saturation class, linearized flag and local coordinate tt[e]; the value tree reduces
+ * dimension 0 first and N - 1 last with the 1-D node I_e; the derivative node D_e works on I_e's four inputs from the very
+ * c1, c2, c3 (k1) that I_e computes:
+ *   Hermite arms     e2 = c2 + c2; e3 = ((1 + 1) + 1) * c3; s = e3.mul_add(tt, e2).mul_add(tt, c1)  (c1 + tt * (e2 + tt * e3))
+ *   linearized arms  s = k1        (the value there is k1.mul_add(tt - 1, y1))
+ *   component d      levels e < d: the value's partial results; level d: D_d; levels e > d: I_e; one scalar s_d remains
+ *   grad[d]          = (Low class along d ? -s_d : s_d) / h[d], one division; h[d] = steps[d], or the spacing the arm's t
+ *                    was divided by on a rectilinear grid (h12: None, h01: Low, h23: High)
+ * every operation rounded in the element type.  It is the derivative of the polynomial piece the value uses: under
+ * linearized extrapolation the held edge slope, without it the extended edge polynomial's; at a knot the piece the
+ * reference's cell rule selects; inside the grid continuous across knots along its own axis in exact arithmetic.
+ * Non-finite inputs propagate.
+ * Arguments, checks, statuses and the first-failing-index contract are those of interpn_hip_eval_grad_device / _host (the
+ * shared check is interpn_hip_eval_host's: a wrong number of coordinate arrays on a multicubic handle of at most 4 dimensions
+ * is INTERPN_HIP_ERR_REFERENCE_PANIC as there, "Dimension mismatch" otherwise); a handle of any other method returns
+ * INTERPN_HIP_ERR_UNSUPPORTED before any device work.
+ * The device form is ONE kernel for every batch size (capturable into a graph; the binned, column and sweep paths have no
+ * gradient form), reported by interpn_hip_kernel_name: "interpn::k_cubic_grad<...>" for N = 2, 3 on the handle's tiled
+ * table, "interpn::k_cubic_grad_n<...>" (runtime N on the C-ordered grid, not tuned) for N = 1, N = 4..8, handles without a
+ * table and option force_generic. */
+int interpn_hip_eval_cubic_grad_device(interpn_hip_interp* h, const void* const* obs, size_t nobs, void* out,
+                                       void* const* grad, size_t npoints, void* stream);
+int interpn_hip_eval_cubic_grad_host(interpn_hip_interp* h, const void* const* obs, const size_t* obs_lens, size_t nobs,
+                                     void* out, size_t nout, void* const* grad);
 
 /* The same evaluation, telling the caller which path it took.
  *   flags        INTERPN_HIP_EVAL_NO_ALLOC: never allocate (scratch that interpn_hip_reserve has

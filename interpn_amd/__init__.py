@@ -185,17 +185,25 @@ def interpn_grad(
     grids: Sequence,
     vals,
     *,
+    method: str = "linear",
+    linearize_extrapolation: bool = True,
     assume_regular: bool = False,
     check_bounds: bool = False,
     bounds_atol: float = 1e-8,
 ):
-    """Multilinear value and gradient at the observation points in one pass: returns `(out, grad)`, `out` shaped like
+    """Multilinear (or, with `method="cubic"`, multicubic) value and gradient at the observation points in one pass: returns `(out, grad)`, `out` shaped like
     `obs[0]` with the bits of `interpn(obs, grids, vals, method="linear")`, `grad` of shape `(N, *obs[0].shape)` with
     `grad[d]` the derivative of the interpolant with respect to coordinate d — the slope of the cell the value uses
     (outside the grid: of the linear extrapolation).  Arrays for numpy points, tensors for torch CUDA points.
 
     The rules are those of `interpn()`: inputs ravelled, dtype from `vals`, regular iff every spacing is exactly equal or
-    `assume_regular`.  Linear only: the multicubic gradient is not built."""
+    `assume_regular`.  `method="cubic"`: the value is `interpn(..., method="cubic", linearize_extrapolation=...)` and the
+    gradient that of the C1 Hermite piece the value uses (DESIGN.md "Multicubic gradients"); `linearize_extrapolation` has no
+    effect on the linear method."""
+    if method not in ("linear", "cubic"):
+        raise ValueError(f"interpn_grad: method must be \"linear\" or \"cubic\", got {method!r}")
+    cubic = method == "cubic"
+    lin = bool(linearize_extrapolation) if cubic else False
     obs = list(obs)
     grids = [np.ascontiguousarray(np.asarray(x).ravel()) for x in grids]
     on_device = bool(obs) and _is_cuda_tensor(obs[0])
@@ -219,9 +227,9 @@ def interpn_grad(
         dims = [len(g) for g in grids]
         starts = np.array([g[0] for g in grids], dtype=dtype)
         steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-        it = Interpolator.regular("linear", dims, starts, steps, vals, device=device, dtype=dtype)
+        it = Interpolator.regular(method, dims, starts, steps, vals, linearize_extrapolation=lin, device=device, dtype=dtype)
     else:
-        it = Interpolator.rectilinear("linear", grids, vals, device=device, dtype=dtype)
+        it = Interpolator.rectilinear(method, grids, vals, linearize_extrapolation=lin, device=device, dtype=dtype)
     try:
         if check_bounds:
             if on_device:
@@ -237,10 +245,10 @@ def interpn_grad(
             if violated:
                 raise ValueError("Observation points violate interpolator bounds")
         if on_device:
-            out, grad = it.eval_grad_tensors(flat)
+            out, grad = (it.eval_cubic_grad_tensors if cubic else it.eval_grad_tensors)(flat)
             it.finish()
         else:
-            out, grad = it.eval_grad_host(flat)
+            out, grad = (it.eval_cubic_grad_host if cubic else it.eval_grad_host)(flat)
     finally:
         it.close()
     return out.reshape(shape), grad.reshape((len(flat),) + shape)

@@ -149,6 +149,8 @@ def load() -> ctypes.CDLL:
                                                  c_void_p]
     lib.interpn_hip_eval_grad_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_size_t,
                                                POINTER(c_void_p)]
+    lib.interpn_hip_eval_cubic_grad_device.argtypes = lib.interpn_hip_eval_grad_device.argtypes
+    lib.interpn_hip_eval_cubic_grad_host.argtypes = lib.interpn_hip_eval_grad_host.argtypes
     lib.interpn_hip_reserve.argtypes = [c_void_p, c_size_t, c_int]
     lib.interpn_hip_stage_ms.argtypes = [c_void_p, POINTER(c_double), c_size_t]
     lib.interpn_hip_check_bounds_device.argtypes = [c_void_p, POINTER(c_void_p), c_size_t, c_size_t, ctypes.c_double,

@@ -1,8 +1,9 @@
-"""A multilinear `Interpolator` as a differentiable function of the observation coordinates.
+"""A multilinear or multicubic `Interpolator` as a differentiable function of the observation coordinates.
 
 `interp(it, obs)` evaluates `it` at the points given as torch CUDA tensors and takes part in torch's autograd: the
 backward pass multiplies the incoming gradient by the derivative of the interpolant with respect to each coordinate,
-which the forward pass computed in the same kernel (`Interpolator.eval_grad_tensors`).  The table is a constant of the
+which the forward pass computed in the same kernel (`Interpolator.eval_grad_tensors`, or `eval_cubic_grad_tensors` for a
+handle whose `method` is "cubic").  The table is a constant of the
 graph: the gradient with respect to `vals` is not built.
 
 torch is imported on first use, and this module is not imported by `import interpn_amd`.
@@ -25,7 +26,8 @@ def _function():
         def forward(ctx, it, *obs):
             shape = obs[0].shape
             flat = [o.detach().reshape(-1).contiguous() for o in obs]
-            out, grad = it.eval_grad_tensors(flat)
+            cubic = getattr(it, "method", None) == "cubic"
+            out, grad = (it.eval_cubic_grad_tensors if cubic else it.eval_grad_tensors)(flat)
             it.finish()
             ctx.save_for_backward(grad)
             ctx.obs_shape = shape
@@ -45,6 +47,6 @@ def _function():
 
 
 def interp(it, obs):
-    """Value of the multilinear interpolator `it` at `obs` (a sequence of N equally shaped torch CUDA tensors of the
+    """Value of the multilinear or multicubic interpolator `it` at `obs` (a sequence of N equally shaped torch CUDA tensors of the
     handle's dtype), differentiable with respect to every tensor of `obs`."""
     return _function().apply(it, *obs)

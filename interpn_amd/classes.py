@@ -91,7 +91,7 @@ class _Base:
             raise TypeError(f"Unexpected data type: {dtype}")
         return self._interp().eval_lattice_host([np.ascontiguousarray(np.asarray(a).ravel()) for a in axes], out)
 
-    def eval_grad(self, obs, out=None, grad=None):
+    def eval_grad(self, obs, out=None, grad=None, _cubic=False):
         """Value and gradient at observation points (numpy arrays or torch CUDA tensors like `eval`): returns
         `(out, grad)`, `out` with the bits of `eval` and `grad[d]` the derivative of the interpolant with respect to
         coordinate d, shape `(N, *obs[0].shape)`.  Multilinear classes only: the others raise the library's
@@ -99,9 +99,10 @@ class _Base:
         obs = list(obs)
         if obs and _is_tensor(obs[0]):
             shape = tuple(obs[0].shape)
-            res, g = self._interp().eval_grad_tensors([o.reshape(-1).contiguous() for o in obs],
-                                                      None if out is None else out.reshape(-1),
-                                                      None if grad is None else grad.reshape(len(obs), -1))
+            it = self._interp()
+            call = it.eval_cubic_grad_tensors if _cubic else it.eval_grad_tensors
+            res, g = call([o.reshape(-1).contiguous() for o in obs], None if out is None else out.reshape(-1),
+                          None if grad is None else grad.reshape(len(obs), -1))
             self._interp().finish()
             return res.reshape(shape), g.reshape((len(obs),) + shape)
         dtype = self.vals.dtype
@@ -109,8 +110,9 @@ class _Base:
             raise TypeError(f"Unexpected data type: {dtype}")
         shape = np.asarray(obs[0]).shape if obs else (0,)
         flat = [np.ascontiguousarray(np.asarray(o).ravel()) for o in obs]
-        res, g = self._interp().eval_grad_host(flat, None if out is None else out.reshape(-1),
-                                               None if grad is None else grad.reshape(len(obs), -1))
+        it = self._interp()
+        call = it.eval_cubic_grad_host if _cubic else it.eval_grad_host
+        res, g = call(flat, None if out is None else out.reshape(-1), None if grad is None else grad.reshape(len(obs), -1))
         return res.reshape(shape), g.reshape((len(obs),) + tuple(shape))
 
     def eval_points(self, pts, out=None):
@@ -338,6 +340,11 @@ class MulticubicRegular(_RegularBase):
     def __init__(self, dims, starts, steps, vals, linearize_extrapolation=True):
         super().__init__(dims, starts, steps, vals, linearize_extrapolation=bool(linearize_extrapolation))
 
+    def eval_cubic_grad(self, obs, out=None, grad=None):
+        """Value and gradient at observation points, like the multilinear classes' `eval_grad`: `grad[d]` is the derivative
+        of the Hermite piece the value uses with respect to coordinate d (DESIGN.md "Multicubic gradients")."""
+        return self.eval_grad(obs, out, grad, _cubic=True)
+
     @classmethod
     def new(cls, dims, starts, steps, vals, linearize_extrapolation: bool = True) -> "MulticubicRegular":
         dtype = vals.dtype
@@ -353,6 +360,11 @@ class MulticubicRectilinear(_RectilinearBase):
 
     def __init__(self, grids, vals, linearize_extrapolation=True):
         super().__init__(grids, vals, linearize_extrapolation=bool(linearize_extrapolation))
+
+    def eval_cubic_grad(self, obs, out=None, grad=None):
+        """Value and gradient at observation points, like the multilinear classes' `eval_grad`: `grad[d]` is the derivative
+        of the Hermite piece the value uses with respect to coordinate d (DESIGN.md "Multicubic gradients")."""
+        return self.eval_grad(obs, out, grad, _cubic=True)
 
     @classmethod
     def new(cls, grids, vals, linearize_extrapolation: bool = True) -> "MulticubicRectilinear":

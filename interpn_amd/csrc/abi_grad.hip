@@ -1,4 +1,6 @@
-// Value and gradient of a multilinear handle: interpn_hip_eval_grad_device / _host.  (C ABI internals, see abi_internal.h.)
+// Value and gradient of a multilinear handle (interpn_hip_eval_grad_device / _host) and of a multicubic handle
+// (interpn_hip_eval_cubic_grad_device / _host): one set of checks and one host chunk loop, the method picks the launcher.
+// (C ABI internals, see abi_internal.h.)
 #include "abi_internal.h"
 
 using namespace interpn;
@@ -19,11 +21,11 @@ struct PoolBlock {
 };
 
 // The checks of interpn_hip_eval_device / _host, with the gradient arrays; 0 = go on
-int grad_checks(interpn_hip_interp* h, const void* const* obs, const size_t* obs_lens, bool need_lens, size_t nobs, void* out,
-                void* const* grad, size_t npoints, bool* nothing) {
+int grad_checks(interpn_hip_interp* h, int method, const void* const* obs, const size_t* obs_lens, bool need_lens, size_t nobs,
+                void* out, void* const* grad, size_t npoints, bool* nothing) {
   *nothing = false;
   if (!h || (!obs && nobs) || (need_lens && !obs_lens && nobs)) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
-  if (h->desc.method != kLinear) return INTERPN_HIP_ERR_UNSUPPORTED;  // cubic, nearest, one_dim: no gradient form
+  if (h->desc.method != method) return INTERPN_HIP_ERR_UNSUPPORTED;  // each entry point serves one method; nearest, one_dim: no gradient form
   const int st = validate_obs(h->desc, obs_lens, nobs, npoints);
   if (st) return st;
   if (npoints == 0) { *nothing = true; return INTERPN_HIP_OK; }
@@ -33,28 +35,30 @@ int grad_checks(interpn_hip_interp* h, const void* const* obs, const size_t* obs
   return INTERPN_HIP_OK;
 }
 
-}  // namespace
+hipError_t launch_grad(const GridDesc& g, const void* const* obs, void* out, void* const* grad, size_t npts,
+                       unsigned long long* first_bad, hipStream_t stream) {
+  return g.method == kCubic ? launch_cubic_grad(g, obs, out, grad, npts, first_bad, stream)
+                            : launch_linear_grad(g, obs, out, grad, npts, first_bad, stream);
+}
 
-extern "C" {
-
-int interpn_hip_eval_grad_device(interpn_hip_interp* h, const void* const* obs, size_t nobs, void* out, void* const* grad,
-                                 size_t npoints, void* stream) {
+int grad_device(interpn_hip_interp* h, int method, const void* const* obs, size_t nobs, void* out, void* const* grad,
+                size_t npoints, void* stream) {
   bool nothing = false;
-  const int st = grad_checks(h, obs, nullptr, false, nobs, out, grad, npoints, &nothing);
+  const int st = grad_checks(h, method, obs, nullptr, false, nobs, out, grad, npoints, &nothing);
   if (st || nothing) return st;
   DeviceGuard guard(h->device);
   if (!guard.ok()) return INTERPN_HIP_ERR_NO_DEVICE;
-  HIP_TRY(launch_linear_grad(h->desc, obs, out, grad, npoints, h->first_bad, static_cast<hipStream_t>(stream)));
+  HIP_TRY(launch_grad(h->desc, obs, out, grad, npoints, h->first_bad, static_cast<hipStream_t>(stream)));
   h->desc.last_binned = 0;
   h->evals_in_place.fetch_add(1);
   mark_stream(h, static_cast<hipStream_t>(stream));
   return INTERPN_HIP_OK;
 }
 
-int interpn_hip_eval_grad_host(interpn_hip_interp* h, const void* const* obs, const size_t* obs_lens, size_t nobs, void* out,
-                               size_t nout, void* const* grad) {
+int grad_host(interpn_hip_interp* h, int method, const void* const* obs, const size_t* obs_lens, size_t nobs, void* out, size_t nout,
+              void* const* grad) {
   bool nothing = false;
-  const int st0 = grad_checks(h, obs, obs_lens, true, nobs, out, grad, nout, &nothing);
+  const int st0 = grad_checks(h, method, obs, obs_lens, true, nobs, out, grad, nout, &nothing);
   if (st0 || nothing) return st0;
   std::lock_guard<std::mutex> host_lock(h->host_mu);
   DeviceGuard guard(h->device);
@@ -84,7 +88,7 @@ int interpn_hip_eval_grad_host(interpn_hip_interp* h, const void* const* obs, co
     const size_t count = (nout - begin) < chunk ? (nout - begin) : chunk;
     for (int d = 0; d < nd; ++d)
       HIP_TRY(hipMemcpyAsync(const_cast<void*>(dev_obs[d]), (const char*)obs[d] + begin * elem, count * elem, hipMemcpyHostToDevice, l.stream));
-    HIP_TRY(launch_linear_grad(h->desc, dev_obs, l.out, dev_grad, count, l.flag_dev, l.stream));
+    HIP_TRY(launch_grad(h->desc, dev_obs, l.out, dev_grad, count, l.flag_dev, l.stream));
     HIP_TRY(hipMemcpyAsync(l.flag_host, l.flag_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, l.stream));
     HIP_TRY(hipStreamSynchronize(l.stream));
     const unsigned long long bad = *l.flag_host;
@@ -102,6 +106,30 @@ int interpn_hip_eval_grad_host(interpn_hip_interp* h, const void* const* obs, co
     if (bad != kNoBadIndexHost) return h->desc.unrep_status;
   }
   return INTERPN_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int interpn_hip_eval_grad_device(interpn_hip_interp* h, const void* const* obs, size_t nobs, void* out, void* const* grad,
+                                 size_t npoints, void* stream) {
+  return grad_device(h, kLinear, obs, nobs, out, grad, npoints, stream);
+}
+
+int interpn_hip_eval_grad_host(interpn_hip_interp* h, const void* const* obs, const size_t* obs_lens, size_t nobs, void* out,
+                               size_t nout, void* const* grad) {
+  return grad_host(h, kLinear, obs, obs_lens, nobs, out, nout, grad);
+}
+
+int interpn_hip_eval_cubic_grad_device(interpn_hip_interp* h, const void* const* obs, size_t nobs, void* out, void* const* grad,
+                                       size_t npoints, void* stream) {
+  return grad_device(h, kCubic, obs, nobs, out, grad, npoints, stream);
+}
+
+int interpn_hip_eval_cubic_grad_host(interpn_hip_interp* h, const void* const* obs, const size_t* obs_lens, size_t nobs, void* out,
+                                     size_t nout, void* const* grad) {
+  return grad_host(h, kCubic, obs, obs_lens, nobs, out, nout, grad);
 }
 
 }  // extern "C"

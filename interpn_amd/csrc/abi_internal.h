@@ -10,7 +10,7 @@
 //   abi_host.hip      host-pointer pipeline, small-batch path, finish, one-shot entry points
 //   abi_bounds.hip    check_bounds
 //   abi_sharded.hip   single-process multi-GPU forms
-//   abi_grad.hip      value and gradient of a multilinear handle (eval_grad_device / _host)
+//   abi_grad.hip      value and gradient of a multilinear or multicubic handle (eval_grad_* / eval_cubic_grad_*)
 //   abi_points.hip    point-major observation points (eval_points_device / _host, reserve_points)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,6 +39,10 @@ namespace interpn {
 // pointers.  The fused kernel for N = 2, 3 on the handle's re-laid table, the runtime-N kernel on `vals` otherwise.
 hipError_t launch_linear_grad(const GridDesc& g, const void* const* obs, void* out, void* const* grad, size_t npts,
                               unsigned long long* first_bad, hipStream_t stream);
+// Multicubic value and gradient in one pass (k_cubic_grad.hip, cubic_grad.h), same arguments: the fused kernel for N = 2, 3
+// on the handle's tiled table, the runtime-N kernel on `vals` otherwise.
+hipError_t launch_cubic_grad(const GridDesc& g, const void* const* obs, void* out, void* const* grad, size_t npts,
+                             unsigned long long* first_bad, hipStream_t stream);
 // Point-major observation points (k_linear_points.hip, linear_points.h): coordinate d of point i at pts[i * stride + d].
 // The fused kernel (N = 2, 3 multilinear on the handle's re-laid table); the de-interleaving of a slice into ndims
 // coordinate arrays (`dst`: host array of device pointers); and the two one-lane kernels around a slice that starts at

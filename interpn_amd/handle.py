@@ -27,6 +27,7 @@ class Interpolator:
         # Streams that evaluations were enqueued on since the last finish(): raw handle -> the
         # object that owns it (a torch Stream kept alive here; None for a caller-supplied integer).
         self._pending_streams = {}
+        self.method = None           # "linear" | "cubic" | "nearest" for handles made by regular() / rectilinear(); kept by replicate()
         self.last_path = None        # "in_place" | "binned" | "sweep": what the most recent device evaluation did
         self.last_path_reason = ""   # why a handle that can sort its points did not
 
@@ -74,7 +75,9 @@ class Interpolator:
             starts.size, steps.ctypes.data_as(POINTER(ct)), steps.size, vptr, nvals, mem,
             int(bool(linearize_extrapolation)), int(device), ctypes.byref(h))
         _lib.raise_for_status(st)
-        return cls(h.value, dtype, nd, keep if mem == _lib.MEM_DEVICE else None)
+        it = cls(h.value, dtype, nd, keep if mem == _lib.MEM_DEVICE else None)
+        it.method = method
+        return it
 
     @classmethod
     def rectilinear(cls, method: str, grids, vals, linearize_extrapolation: bool = False, device: int = -1,
@@ -89,7 +92,9 @@ class Interpolator:
             cls._method_arg(method, fma), gptr, glen, ng, vptr, nvals, mem,
             int(bool(linearize_extrapolation)), int(device), ctypes.byref(h))
         _lib.raise_for_status(st)
-        return cls(h.value, dtype, ng, keep if mem == _lib.MEM_DEVICE else None)
+        it = cls(h.value, dtype, ng, keep if mem == _lib.MEM_DEVICE else None)
+        it.method = method
+        return it
 
     @classmethod
     def grid1d_regular(cls, method: str, start, step, vals, device: int = -1, dtype=None, fma=None) -> "Interpolator":
@@ -135,7 +140,9 @@ class Interpolator:
         (`interpn_hip_replicate`); the clone owns its copy."""
         h = c_void_p()
         _lib.raise_for_status(_lib.load().interpn_hip_replicate(self._h, int(device), ctypes.byref(h)))
-        return Interpolator(h.value, self.dtype, self._ndims)
+        it = Interpolator(h.value, self.dtype, self._ndims)
+        it.method = self.method
+        return it
 
     # -- evaluation -----------------------------------------------------------------------
     def ndims(self) -> int:
@@ -274,7 +281,7 @@ class Interpolator:
         return out
 
     # -- value and gradient (multilinear handles) --------------------------------------------
-    def eval_grad_host(self, obs, out: np.ndarray = None, grad: np.ndarray = None):
+    def eval_grad_host(self, obs, out: np.ndarray = None, grad: np.ndarray = None, _entry="interpn_hip_eval_grad_host"):
         """Value and gradient on host arrays (synchronous; `interpn_hip_eval_grad_host`): returns `(out, grad)` with
         `out[i]` the bits of `eval_host` and `grad[d, i]` the derivative of the interpolant with respect to coordinate d
         at point i (shape `(N, n)`), the slope of the cell the value path selects.  Multilinear handles only; on
@@ -302,11 +309,11 @@ class Interpolator:
         for i in range(nobs):
             vp[i] = ctypes.cast(optr[i], c_void_p)
             gp[i] = c_void_p(grad[i].ctypes.data)
-        st = lib.interpn_hip_eval_grad_host(self._h, vp, olen, nobs, out.ctypes.data_as(c_void_p), out.size, gp)
+        st = getattr(lib, _entry)(self._h, vp, olen, nobs, out.ctypes.data_as(c_void_p), out.size, gp)
         _lib.raise_for_status(st)
         return out, grad
 
-    def eval_grad_tensors(self, obs, out=None, grad=None, stream=None):
+    def eval_grad_tensors(self, obs, out=None, grad=None, stream=None, _entry="interpn_hip_eval_grad_device"):
         """The same on torch CUDA tensors (`interpn_hip_eval_grad_device`): one kernel, asynchronous like `eval_tensors`
         and capturable into a graph; `grad` is a tensor of shape `(N, n)` whose rows are contiguous.  `finish()`
         synchronises and surfaces "Unrepresentable coordinate value"."""
@@ -344,10 +351,20 @@ class Interpolator:
         k = len(obs)
         vp = (c_void_p * max(k, 1))(*[t.data_ptr() for t in obs])
         gp = (c_void_p * max(k, 1))(*[grad[d].data_ptr() for d in range(k)])
-        st = _lib.load().interpn_hip_eval_grad_device(self._h, vp, k, c_void_p(out.data_ptr()), gp, n, c_void_p(int(raw)))
+        st = getattr(_lib.load(), _entry)(self._h, vp, k, c_void_p(out.data_ptr()), gp, n, c_void_p(int(raw)))
         _lib.raise_for_status(st)
         self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
         return out, grad
+
+    # -- value and gradient (multicubic handles) ----------------------------------------------
+    def eval_cubic_grad_host(self, obs, out: np.ndarray = None, grad: np.ndarray = None):
+        """`eval_grad_host` for multicubic handles (`interpn_hip_eval_cubic_grad_host`): `grad[d, i]` is the derivative of
+        the Hermite piece the value uses (DESIGN.md "Multicubic gradients"); every other handle raises "unsupported"."""
+        return self.eval_grad_host(obs, out, grad, _entry="interpn_hip_eval_cubic_grad_host")
+
+    def eval_cubic_grad_tensors(self, obs, out=None, grad=None, stream=None):
+        """`eval_grad_tensors` for multicubic handles (`interpn_hip_eval_cubic_grad_device`): one kernel, capturable."""
+        return self.eval_grad_tensors(obs, out, grad, stream, _entry="interpn_hip_eval_cubic_grad_device")
 
     # -- point-major observation points (one array of shape (n, N)) ---------------------------
     def last_points_path(self):
