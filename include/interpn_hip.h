@@ -697,6 +697,65 @@ int interpn_hip_eval_points_host(interpn_hip_interp* h, const void* pts, size_t 
  * Synchronous.  (A slice that the handle would sort or sweep takes a second block: interpn_hip_reserve.) */
 int interpn_hip_reserve_points(interpn_hip_interp* h, size_t npoints, int nstreams);
 
+/* ------------------------------------------------------------------------------------------
+ * Point-major gradients — value and d/dx of an (npoints, N) positions array in one pass, the gradient in the same layout:
+ * what a differentiable model, a particle pusher, a ray marcher or a Newton step on a table holds and wants back.
+ *
+ * Definition  input block: `pts`, `npoints`, `point_stride` >= ndims in ELEMENTS as above; coordinate d of point i is
+ *           pts[i * point_stride + d].  Value: `out`, npoints contiguous elements.  Gradient block: `grad` and a
+ *           `grad_stride` >= ndims in ELEMENTS; component d of point i goes to grad[i * grad_stride + d].  Elements
+ *           d >= ndims of a gradient row are never written and the last row's need not exist: g[:, :3] of an (n, 4) array
+ *           is taken as it is.  `pts` and `grad` must not overlap.
+ * Contract  multilinear handle: out[i] and grad[i, d] have exactly the bits interpn_hip_eval_grad_device gives on the N
+ *           de-interleaved coordinate arrays; multicubic handle: exactly the bits of interpn_hip_eval_cubic_grad_device —
+ *           for every kind, N = 1..8, f64 and f32, both fma flavours and both linearize_extrapolation settings.  One pair
+ *           of entry points serves both methods: the handle's method picks.  Nearest and one_dim handles:
+ *           INTERPN_HIP_ERR_UNSUPPORTED before any device work.
+ * Paths     FUSED, multilinear N = 2, 3 on a handle with a re-laid table: interpn::k_linear_points_grad — the coordinate
+ *           load of k_linear_points (option "points_load"), the arithmetic of k_linear_grad, and a gradient-row store in
+ *           one of three forms: packed rows (grad_stride == N) whose base is aligned to two elements as per-lane vector
+ *           stores of the lane's own PPL * N consecutive elements; (3-D f64, two points per lane) the wave's whole span
+ *           through LDS as lane-contiguous 16-byte stores; anything else element by element.  Two points per lane
+ *           need `out` aligned to two elements.  The kernel addresses a workgroup's rows by 32-bit offsets: it takes
+ *           point_stride and grad_stride of up to 2^20 ELEMENTS each; longer rows go to the split path.
+ *           FUSED, multicubic N = 2, 3 on a handle with its tiled table: interpn::k_cubic_points_grad — k_cubic_grad
+ *           reading the point's row and storing to the point's gradient row, one point per lane.
+ *           Either is one launch, uses no scratch, allocates nothing and is capturable.
+ *           DIRECT (N = 1 with both strides 1): the blocks are a coordinate and a component array; the column form's
+ *           launch, no copy.
+ *           SPLIT (everything else: N = 1 with a stride, N >= 4, handles without a re-laid table, option force_generic,
+ *           a multilinear handle with point_stride or grad_stride above 2^20 elements, "points_path" = 2): per slice interpn::k_split_points de-interleaves the rows into scratch, the column form's
+ *           launch writes the value to `out` and the N components to scratch, interpn::k_join_grad interleaves them into
+ *           the gradient rows.
+ * Options   "points_path", "points_load", "points_slice" as above.  "points_store" = 0 automatic (the fastest measured
+ *           form: 2 in 3-D f64 with two points per lane, 1 for other packed, aligned rows, else 3), 1 per-lane vector
+ *           stores, 2 (3-D f64) the span through LDS, 3 element stores.  Read-only
+ *           "last_points_path".  interpn_hip_kernel_name reports "interpn::k_linear_points_grad<...>" or
+ *           "interpn::k_cubic_points_grad<...>" after a fused evaluation, the column form's kernel otherwise.
+ * Scratch   the split path under the rules above; a slice needs N coordinate and N component arrays:
+ *           interpn_hip_reserve_points_grad sizes blocks for that.
+ * Checks    before any device work, in this order: h NULL: INTERPN_HIP_ERR_INVALID_ARGUMENT; a handle that is neither
+ *           multilinear nor multicubic: INTERPN_HIP_ERR_UNSUPPORTED; point_stride < ndims or grad_stride < ndims:
+ *           INTERPN_HIP_ERR_INVALID_ARGUMENT; npoints == 0: INTERPN_HIP_OK whatever the pointers are; pts, out or grad
+ *           NULL: INTERPN_HIP_ERR_INVALID_ARGUMENT; a block whose bytes overflow size_t: INTERPN_HIP_ERR_INVALID_ARGUMENT;
+ *           option points_path = 1 on a handle without a fused form, or with rows longer than the fused multilinear
+ *           kernel takes: INTERPN_HIP_ERR_UNSUPPORTED.
+ * Failing   regular grids: interpn_hip_finish reports the first failing index of the whole call (device form); the host
+ * points    form writes exactly out[0..i) and gradient rows [0..i) and leaves everything else as it was.
+ * ---------------------------------------------------------------------------------------- */
+/* Asynchronous on `stream`.  `pts`, `out`, `grad`: device.  `flags`: INTERPN_HIP_EVAL_NO_ALLOC.  *path_taken (may be NULL):
+ * INTERPN_HIP_POINTS_PATH_*. */
+int interpn_hip_eval_points_grad_device(interpn_hip_interp* h, const void* pts, size_t point_stride, size_t npoints,
+                                        void* out, void* grad, size_t grad_stride, void* stream, unsigned flags,
+                                        int* path_taken);
+/* The same on host arrays, synchronous: chunks like interpn_hip_eval_points_host, a chunk's rows uploaded with one copy,
+ * the values and the gradient rows in front of the first failing point downloaded. */
+int interpn_hip_eval_points_grad_host(interpn_hip_interp* h, const void* pts, size_t point_stride, size_t npoints,
+                                      void* out, void* grad, size_t grad_stride);
+/* Scratch blocks for split-path gradient evaluations of up to `npoints` points on up to `nstreams` concurrent streams.
+ * Synchronous. */
+int interpn_hip_reserve_points_grad(interpn_hip_interp* h, size_t npoints, int nstreams);
+
 #ifdef __cplusplus
 }
 #endif

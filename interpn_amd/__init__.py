@@ -43,6 +43,7 @@ __all__ = [
     "interpn_grad",
     "interpn_lattice",
     "interpn_points",
+    "interpn_points_grad",
     "lattice_plan",
     "Fields",
     "fields_layout",
@@ -339,6 +340,87 @@ def interpn_points(
     finally:
         it.close()
     return res.reshape(shape)
+
+
+def interpn_points_grad(
+    xi,
+    grids: Sequence,
+    vals,
+    *,
+    method: str = "linear",
+    linearize_extrapolation: bool = True,
+    assume_regular: bool = False,
+    check_bounds: bool = False,
+    bounds_atol: float = 1e-8,
+):
+    """`interpn_grad()` for points kept as ONE array `xi` of shape `(..., N)`, the gradient in the same layout: returns
+    `(out, grad)` of shapes `xi.shape[:-1]` and `xi.shape` — arrays for a numpy `xi`, tensors for a torch CUDA `xi` — with
+    the bits of `interpn_grad([xi[..., 0], .., xi[..., N-1]], grids, vals, ...)`, `grad[..., d]` being its `grad[d]`.
+    Neither the columns nor the component arrays are made: multilinear and multicubic N = 2, 3 read the rows and write the
+    gradient rows in their one kernel, everything else works on slices on the device.
+
+    The rules are those of `interpn_points()` and `interpn_grad()`: `method` "linear" or "cubic", dtype from `vals` (`xi`
+    must have it), regular iff every spacing is exactly equal or `assume_regular`; `linearize_extrapolation` has no
+    effect on the linear method; `check_bounds` unstacks the columns for the existing check."""
+    if method not in ("linear", "cubic"):
+        raise ValueError(f"interpn_points_grad: method must be \"linear\" or \"cubic\", got {method!r}")
+    lin = bool(linearize_extrapolation) if method == "cubic" else False
+    on_device = _is_cuda_tensor(xi)
+    if not on_device:
+        xi = np.asarray(xi)
+    if len(xi.shape) < 1 or xi.shape[-1] != len(grids):
+        raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+    if not (_is_cuda_tensor(vals) or isinstance(vals, np.ndarray)):
+        raise TypeError("argument 'vals': expected a numpy array or a torch tensor")
+    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
+    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
+    vals = vals.reshape(-1).contiguous() if _is_cuda_tensor(vals) else np.ascontiguousarray(vals.ravel())
+    grids = [np.ascontiguousarray(np.asarray(x).ravel()).astype(dtype, copy=False) for x in grids]
+    shape = tuple(xi.shape[:-1])
+    n = len(grids)
+    device = -1
+    if on_device:
+        import torch
+
+        device = xi.device.index if xi.device.index is not None else torch.cuda.current_device()
+        flat = xi if xi.dim() == 2 else xi.reshape(-1, n)
+        if n > 1 and flat.stride(1) != 1:
+            flat = flat.contiguous()
+    else:
+        flat = xi if xi.ndim == 2 else xi.reshape(-1, n)
+        if n > 1 and flat.strides[1] != flat.itemsize:
+            flat = np.ascontiguousarray(flat)
+    is_regular = assume_regular or _check_regular(grids)
+    if is_regular:
+        dims = [len(g) for g in grids]
+        starts = np.array([g[0] for g in grids], dtype=dtype)
+        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
+        it = Interpolator.regular(method, dims, starts, steps, vals, linearize_extrapolation=lin, device=device, dtype=dtype)
+    else:
+        it = Interpolator.rectilinear(method, grids, vals, linearize_extrapolation=lin, device=device, dtype=dtype)
+    try:
+        if check_bounds:
+            if on_device:
+                violated = it.check_bounds_tensors([flat[:, d].contiguous() for d in range(n)], bounds_atol).any()
+            else:
+                sfx = "f64" if dtype == np.float64 else "f32"
+                cols = [np.ascontiguousarray(flat[:, d]) for d in range(n)]
+                outb = np.zeros(n, dtype=bool)
+                if is_regular:
+                    getattr(raw, f"check_bounds_regular_{sfx}")(dims, starts, steps, cols, bounds_atol, outb)
+                else:
+                    getattr(raw, f"check_bounds_rectilinear_{sfx}")(grids, cols, bounds_atol, outb)
+                violated = any(outb)
+            if violated:
+                raise ValueError("Observation points violate interpolator bounds")
+        if on_device:
+            res, grad = it.eval_points_grad_tensors(flat)
+            it.finish()
+        else:
+            res, grad = it.eval_points_grad_host(flat)
+    finally:
+        it.close()
+    return res.reshape(shape), grad.reshape(shape + (n,))
 
 
 def interpn_lattice(

@@ -192,6 +192,10 @@ def load() -> ctypes.CDLL:
                                                    POINTER(c_int)]
     lib.interpn_hip_eval_points_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
     lib.interpn_hip_reserve_points.argtypes = [c_void_p, c_size_t, c_int]
+    lib.interpn_hip_eval_points_grad_device.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t,
+                                                        c_void_p, ctypes.c_uint, POINTER(c_int)]
+    lib.interpn_hip_eval_points_grad_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t]
+    lib.interpn_hip_reserve_points_grad.argtypes = [c_void_p, c_size_t, c_int]
     _lib = lib
     return lib
 

@@ -6,12 +6,16 @@ which the forward pass computed in the same kernel (`Interpolator.eval_grad_tens
 handle whose `method` is "cubic").  The table is a constant of the
 graph: the gradient with respect to `vals` is not built.
 
+`interp_points(it, pts)` is the same for positions kept as ONE tensor of shape `(..., N)`: its forward pass is one
+`Interpolator.eval_points_grad_tensors`, and `pts.grad` has the shape of `pts`.
+
 torch is imported on first use, and this module is not imported by `import interpn_amd`.
 """
 
 from __future__ import annotations
 
 _FUNCTION = None
+_POINTS_FUNCTION = None
 
 
 def _function():
@@ -50,3 +54,38 @@ def interp(it, obs):
     """Value of the multilinear or multicubic interpolator `it` at `obs` (a sequence of N equally shaped torch CUDA tensors of the
     handle's dtype), differentiable with respect to every tensor of `obs`."""
     return _function().apply(it, *obs)
+
+
+def _points_function():
+    """The point-major torch.autograd.Function, built on first use like `_function`."""
+    global _POINTS_FUNCTION
+    if _POINTS_FUNCTION is not None:
+        return _POINTS_FUNCTION
+    import torch
+
+    class _InterpPoints(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, it, pts):
+            shape = pts.shape
+            flat = pts.detach().reshape(-1, shape[-1])
+            if flat.shape[1] > 1 and flat.stride(1) != 1:
+                flat = flat.contiguous()
+            out, grad = it.eval_points_grad_tensors(flat)
+            it.finish()
+            ctx.save_for_backward(grad)
+            ctx.pts_shape = shape
+            return out.reshape(shape[:-1])
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            (grad,) = ctx.saved_tensors
+            return None, (grad_out.reshape(-1).unsqueeze(-1) * grad).reshape(ctx.pts_shape)
+
+    _POINTS_FUNCTION = _InterpPoints
+    return _POINTS_FUNCTION
+
+
+def interp_points(it, pts):
+    """Value of the multilinear or multicubic interpolator `it` at the points `pts`, ONE torch CUDA tensor of shape `(..., N)`
+    of the handle's dtype: the result has shape `pts.shape[:-1]` and is differentiable with respect to `pts`."""
+    return _points_function().apply(it, pts)

@@ -135,6 +135,43 @@ class _Base:
             flat = np.ascontiguousarray(flat)
         return self._interp().eval_points_host(flat, None if out is None else out.reshape(-1)).reshape(shape)
 
+    @staticmethod
+    def _flat_view(buf, shape, what):
+        """A caller's result buffer seen in `shape` WITHOUT a copy: results written into a copy would never reach the
+        caller, so a buffer whose strides do not allow the view is rejected (`reshape` would copy it silently)."""
+        if buf is None:
+            return None
+        try:
+            if _is_tensor(buf):
+                return buf.view(shape)
+            view = np.asarray(buf).view()
+            view.shape = shape
+            return view
+        except (RuntimeError, AttributeError, ValueError) as exc:
+            raise ValueError(f"{what}: a buffer of shape {tuple(buf.shape)} with these strides cannot be viewed as {shape} "
+                             "without a copy; pass a contiguous one") from exc
+
+    def _eval_points_grad(self, pts, out=None, grad=None):
+        shape = tuple(pts.shape[:-1])
+        nd = int(pts.shape[-1])
+        out, grad = self._flat_view(out, (-1,), "out"), self._flat_view(grad, (-1, nd), "grad")
+        if _is_tensor(pts):
+            flat = pts if pts.dim() == 2 else pts.reshape(-1, nd)
+            if flat.shape[1] > 1 and flat.stride(1) != 1:
+                flat = flat.contiguous()
+            res, g = self._interp().eval_points_grad_tensors(flat, out, grad)
+            self._interp().finish()
+            return res.reshape(shape), g.reshape(shape + (nd,))
+        dtype = self.vals.dtype
+        if dtype not in (np.float64, np.float32):
+            raise TypeError(f"Unexpected data type: {dtype}")
+        pts = np.asarray(pts)
+        flat = pts if pts.ndim == 2 else pts.reshape(-1, nd)
+        if flat.shape[1] > 1 and flat.strides[1] != flat.itemsize:
+            flat = np.ascontiguousarray(flat)
+        res, g = self._interp().eval_points_grad_host(flat, out, grad)
+        return res.reshape(shape), g.reshape(shape + (nd,))
+
     def eval_unchecked(self, obs, out=None):
         dtype = self.vals.dtype
         if dtype not in (np.float64, np.float32):
@@ -279,6 +316,12 @@ class MultilinearRegular(_RegularBase):
 
     _method = "linear"
 
+    def eval_points_grad(self, pts, out=None, grad=None):
+        """Value and gradient at points given as ONE array of shape `(..., N)` (numpy, or a torch CUDA tensor like `eval`):
+        returns `(out, grad)` of shapes `pts.shape[:-1]` and `pts.shape`, `grad[..., d]` the derivative with respect to
+        coordinate d, with the bits of `eval_grad` on the N unstacked columns, which are never made."""
+        return self._eval_points_grad(pts, out, grad)
+
     @classmethod
     def new(cls, dims, starts, steps, vals) -> "MultilinearRegular":
         dtype = vals.dtype
@@ -290,6 +333,12 @@ class MultilinearRectilinear(_RectilinearBase):
     """Multilinear interpolation on a rectilinear grid (src/interpn/multilinear_rectilinear.py:24)."""
 
     _method = "linear"
+
+    def eval_points_grad(self, pts, out=None, grad=None):
+        """Value and gradient at points given as ONE array of shape `(..., N)` (numpy, or a torch CUDA tensor like `eval`):
+        returns `(out, grad)` of shapes `pts.shape[:-1]` and `pts.shape`, `grad[..., d]` the derivative with respect to
+        coordinate d, with the bits of `eval_grad` on the N unstacked columns, which are never made."""
+        return self._eval_points_grad(pts, out, grad)
 
     @classmethod
     def new(cls, grids, vals) -> "MultilinearRectilinear":
@@ -345,6 +394,12 @@ class MulticubicRegular(_RegularBase):
         of the Hermite piece the value uses with respect to coordinate d (DESIGN.md "Multicubic gradients")."""
         return self.eval_grad(obs, out, grad, _cubic=True)
 
+    def eval_points_grad(self, pts, out=None, grad=None):
+        """Value and gradient at points given as ONE array of shape `(..., N)` (numpy, or a torch CUDA tensor like `eval`):
+        returns `(out, grad)` of shapes `pts.shape[:-1]` and `pts.shape`, `grad[..., d]` the derivative with respect to
+        coordinate d, with the bits of `eval_cubic_grad` on the N unstacked columns, which are never made."""
+        return self._eval_points_grad(pts, out, grad)
+
     @classmethod
     def new(cls, dims, starts, steps, vals, linearize_extrapolation: bool = True) -> "MulticubicRegular":
         dtype = vals.dtype
@@ -365,6 +420,12 @@ class MulticubicRectilinear(_RectilinearBase):
         """Value and gradient at observation points, like the multilinear classes' `eval_grad`: `grad[d]` is the derivative
         of the Hermite piece the value uses with respect to coordinate d (DESIGN.md "Multicubic gradients")."""
         return self.eval_grad(obs, out, grad, _cubic=True)
+
+    def eval_points_grad(self, pts, out=None, grad=None):
+        """Value and gradient at points given as ONE array of shape `(..., N)` (numpy, or a torch CUDA tensor like `eval`):
+        returns `(out, grad)` of shapes `pts.shape[:-1]` and `pts.shape`, `grad[..., d]` the derivative with respect to
+        coordinate d, with the bits of `eval_cubic_grad` on the N unstacked columns, which are never made."""
+        return self._eval_points_grad(pts, out, grad)
 
     @classmethod
     def new(cls, grids, vals, linearize_extrapolation: bool = True) -> "MulticubicRectilinear":

@@ -35,11 +35,19 @@ int grad_checks(interpn_hip_interp* h, int method, const void* const* obs, const
   return INTERPN_HIP_OK;
 }
 
+}  // namespace
+
+namespace interpn_abi {
+
 hipError_t launch_grad(const GridDesc& g, const void* const* obs, void* out, void* const* grad, size_t npts,
                        unsigned long long* first_bad, hipStream_t stream) {
   return g.method == kCubic ? launch_cubic_grad(g, obs, out, grad, npts, first_bad, stream)
                             : launch_linear_grad(g, obs, out, grad, npts, first_bad, stream);
 }
+
+}  // namespace interpn_abi
+
+namespace {
 
 int grad_device(interpn_hip_interp* h, int method, const void* const* obs, size_t nobs, void* out, void* const* grad,
                 size_t npoints, void* stream) {

@@ -11,7 +11,8 @@
 //   abi_bounds.hip    check_bounds
 //   abi_sharded.hip   single-process multi-GPU forms
 //   abi_grad.hip      value and gradient of a multilinear or multicubic handle (eval_grad_* / eval_cubic_grad_*)
-//   abi_points.hip    point-major observation points (eval_points_device / _host, reserve_points)
+//   abi_points.hip    point-major observation points (eval_points_device / _host, reserve_points) and their gradient form
+//                     (eval_points_grad_device / _host, reserve_points_grad)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,6 +54,13 @@ hipError_t launch_linear_points(const GridDesc& g, const void* pts, size_t strid
 hipError_t launch_split_points(const GridDesc& g, const void* pts, size_t stride, void* const* dst, size_t count, hipStream_t stream);
 hipError_t launch_points_bad_begin(unsigned long long* word, unsigned long long* saved, hipStream_t stream);
 hipError_t launch_points_bad_end(unsigned long long* word, const unsigned long long* saved, unsigned long long begin, hipStream_t stream);
+// Point-major value and gradient (k_points_grad.hip, points_grad.h): component d of point i goes to grad[i * gstride + d].
+// The fused kernels (N = 2, 3: multilinear on the re-laid table, multicubic on the tiled table), and the split path's last
+// step, which interleaves ndims component arrays (`src`: host array of device pointers) into the gradient rows.
+bool points_grad_fused_applies(const GridDesc& g, size_t stride, size_t gstride);
+hipError_t launch_points_grad(const GridDesc& g, const void* pts, size_t stride, void* out, void* grad, size_t gstride, size_t npts,
+                              unsigned long long* first_bad, hipStream_t stream);
+hipError_t launch_join_grad(const GridDesc& g, const void* const* src, void* grad, size_t gstride, size_t count, hipStream_t stream);
 }  // namespace interpn
 
 namespace interpn_abi {
@@ -328,6 +336,11 @@ void claim_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot);
 int reserve_slots(interpn_hip_interp* h, size_t need, int nstreams);
 constexpr size_t kExpandSliceBytes = (size_t)64 << 20;  // coordinates of one slice (bounds the scratch block)
 constexpr size_t kExpandSliceMin = (size_t)1 << 16;     // ... but never fewer points than this
+
+// abi_grad.hip: the column form's gradient launch, k_linear_grad / k_cubic_grad or the runtime-N kernels by the handle's
+// method and each launcher's own rule (also the middle step of the point-major split path, abi_points.hip)
+hipError_t launch_grad(const GridDesc& g, const void* const* obs, void* out, void* const* grad, size_t npts,
+                       unsigned long long* first_bad, hipStream_t stream);
 
 // abi_sweep.hip
 int eval_device_sweep(interpn_hip_interp* h, const void* const* obs, void* out, size_t npoints, hipStream_t stream,

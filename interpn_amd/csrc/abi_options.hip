@@ -47,6 +47,7 @@ bool option_access(LaunchConfig& c, const char* name, long long* value, bool set
       {"lattice", &c.lattice, -1, 1},
       {"points_path", &c.points_path, 0, 2},
       {"points_load", &c.points_load, 0, 3},
+      {"points_store", &c.points_store, 0, 3},
   };
   if (!name || !value) return false;
   if (!strcmp(name, "host_chunk")) {
@@ -98,7 +99,7 @@ bool option_access(LaunchConfig& c, const char* name, long long* value, bool set
 void latch_env(LaunchConfig& c) {
   static const char* const names[] = {"blocks_per_cu", "iters_per_block", "ppl", "axis_regs", "force_generic",
                                       "generic_runtime", "generic_vec", "persistent", "axis_lds_kb", "host_chunk", "binned", "deal",
-                                      "bin_slice_log2", "column", "column_part", "column_threads", "column_groups", "column_cpp", "column_coef", "column_pad", "hist_wgs_per_cu", "column_keys", "column_tail", "scatter_staged", "axis_records", "bin_scramble", "sweep", "sweep_period", "sweep_probe", "gated_iters", "finish_kernel", "lattice", "points_path", "points_load", "points_slice"};
+                                      "bin_slice_log2", "column", "column_part", "column_threads", "column_groups", "column_cpp", "column_coef", "column_pad", "hist_wgs_per_cu", "column_keys", "column_tail", "scatter_staged", "axis_records", "bin_scramble", "sweep", "sweep_period", "sweep_probe", "gated_iters", "finish_kernel", "lattice", "points_path", "points_load", "points_store", "points_slice"};
   for (const char* nm : names) {
     char var[64] = "INTERPN_HIP_";
     size_t k = strlen(var);

@@ -63,6 +63,7 @@ struct LaunchConfig {
   int lattice = -1;        // lattice evaluation (lattice.h): -1 the row kernel where the layout rules of lattice_plan say it pays, 0 never (expand and evaluate), 1 wherever it is covered and its lines fit the LDS budget
   int points_path = 0;     // point-major evaluation (linear_points.h): 0 automatic, 1 the fused kernel or INTERPN_HIP_ERR_UNSUPPORTED, 2 de-interleave and evaluate
   int points_load = 0;     // the fused kernel's coordinate load on packed, aligned rows: 0 automatic (3-D f64: 2, else 1), 1 per-lane vector loads, 2 the wave's span through LDS (3-D f64), 3 element loads
+  int points_store = 0;    // the fused point-major gradient kernel's gradient-row store on packed, aligned rows (points_grad.h): 0 automatic (measured, DESIGN.md section 14: 2 in 3-D f64 with two points per lane, 1 otherwise), 1 per-lane vector stores, 2 the wave's span through LDS (3-D f64), 3 element stores
   long long points_slice = 0;  // testing: points per slice of the split path (0 = 64 MiB of coordinates; rounded down to a multiple of 256)
   int sweep_period = 0;    // sweep evaluation: ticks of 10 ns per sweep of the leading index (0: what the previous launch measured; 1: no clock, rows in sorted order; tests / tuning)
 };

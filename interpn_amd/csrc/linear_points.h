@@ -20,10 +20,9 @@
 #pragma once
 
 #include "linear_grad.h"
+#include "points_forms.h"
 
 namespace interpn {
-
-enum PointsLoad : int { kPointsLoadElem = 0, kPointsLoadWide = 1, kPointsLoadLds = 2 };
 
 template <typename T, int N>
 struct PointsArgs {
@@ -232,8 +231,6 @@ struct SplitArgs {
   int ndims;
   T* dst[kMaxDims];
 };
-
-constexpr size_t kSplitTileStride = 32;  // rows up to this many elements go through the LDS tile
 
 // One workgroup per kBlock points: their rows are kBlock * stride consecutive elements.
 template <typename T>

@@ -1,0 +1,559 @@
+// Point-major value AND gradient: coordinate d of point i is pts[i * stride + d], component d of its gradient goes to
+// grad[i * gstride + d] (an (n, N) positions array in, an (n, N) gradient array out), without de-interleaving the
+// points first or interleaving the components afterwards.
+//
+//   k_linear_points_grad<T, N, RECT, FMA, SI, SJ, PPL, AXR, CELL>   N = 2, 3 multilinear on the re-laid table the handle
+//       already has.  The coordinate load is k_linear_points' (all three forms, PointsGradArgs::load); cell search, t,
+//       the gather, the value tree and the gradient arithmetic are k_linear_grad's statements, so `out` and `grad` have
+//       the bits of interpn_hip_eval_grad_device on the de-interleaved columns.  Only the gradient-row store is new
+//       (PointsGradArgs::store, launch-uniform):
+//         kPointsStoreElem   one element store per component: any stride, any alignment; also the ragged tail
+//         kPointsStoreWide   gstride == N, base aligned to two elements: the lane's own PPL * N contiguous elements as
+//                            two-element vector stores (the mirror of kPointsLoadWide)
+//         kPointsStoreLds    3-D f64 with PPL = 2: every lane writes its 48 bytes into the wave's own part of the piece
+//                            exchange area (idle after the iteration's last gather), the wave stores its 3072-byte span
+//                            as three lane-contiguous 16-byte stores (no LDS beyond what the gather has; waves of the
+//                            ragged tail take the wide form)
+//       Elements d >= N of a gradient row are never written.
+//       A workgroup's rows are addressed by 32-bit offsets from the iteration's uniform first point (the launcher keeps
+//       both strides at or below kPointsGradMaxStride), and two empty `asm volatile` statements pin values where they
+//       are written: the lane index inside the iteration (what is derived from it is otherwise loop invariant, hoisted
+//       and held in registers across the iteration) and the first point's results in front of the second point's gather
+//       (otherwise their arithmetic is sunk behind it and the first cell stays live).  With them every instantiation
+//       keeps the occupancy step of its k_linear_grad counterpart (tests/test_points_grad_cpu.py).  Measured, they buy no
+//       speed: the un-pinned build (INTERPN_POINTS_GRAD_NO_PINS below) ran 1 - 4 % faster per 1e8 points in the four
+//       instantiations that were timed (3-D f64 1.696 against 1.762 ms) and level at 1e6; they stay for the occupancy
+//       requirement, which covers all 180 instantiations.  DESIGN.md section 14.
+//   k_cubic_points_grad<T, N, RECT, FMA, SI, SJ>   N = 2, 3 on the tiled table of a cubic handle: k_cubic_grad with the
+//       coordinates read from the point's row and the N components stored to the point's gradient row; one point per
+//       lane, element accesses, or for N = 2 with packed aligned rows (`vec2`) one two-element vector access each.
+//   k_join_grad<T>   the split path's last step, the mirror of k_split_points: interleaves N component arrays into the
+//       gradient rows through an LDS tile (contiguous reads of every array, contiguous writes of the rows that skip
+//       columns d >= N); rows longer than kSplitTileStride elements: a lane per point.
+#pragma once
+
+#include "cubic_grad.h"
+#include "linear_grad.h"
+#include "points_forms.h"
+
+// The pins of k_linear_points_grad (see above).  INTERPN_POINTS_GRAD_NO_PINS builds the kernel without them, for
+// `make variant` measurements only (DESIGN.md section 14 has the figures); the product is never built that way.
+#ifdef INTERPN_POINTS_GRAD_NO_PINS
+#define INTERPN_POINTS_GRAD_PIN(x) ((void)0)
+#else
+#define INTERPN_POINTS_GRAD_PIN(x) asm volatile("" : "+v"(x))
+#endif
+
+namespace interpn {
+
+template <typename T, int N>
+struct PointsGradArgs {
+  const T* bricks;
+  const T* pts;
+  size_t stride;  // elements from point to point, >= N
+  T* out;
+  T* grad;
+  size_t gstride;  // elements from gradient row to gradient row, >= N
+  unsigned long long* first_bad;
+  size_t npts;
+  int load;   // PointsLoad
+  int store;  // PointsStore
+  T start[N];
+  T step[N];
+  int n[N];
+  AxisArgs<T, N> ax;
+  unsigned nbj, nbk;  // N == 3: bricks along j and k; N == 2: nbj = bricks along j
+  unsigned iters;     // kBlock-wide iterations per workgroup
+};
+
+template <typename T, int N, bool RECT, bool FMA, int SI, int SJ, int PPL, int AXR = 0, int CELL = 0>
+__global__ void __launch_bounds__(kBlock) k_linear_points_grad(const PointsGradArgs<T, N> a) {
+  static_assert(N == 2 || N == 3, "fused point-major gradient kernel: N = 2, 3");
+  static_assert(CELL == 0 || (CELL == 2 && N == 3 && sizeof(T) == 4 && SI == 1 && SJ == 1), "2 x 4 x 4 bricks: 3-D f32");
+  typedef typename LeafVec<T, 2>::type P;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  // N == 3: [pieces][offsets][axes] as in k_linear_brick; N == 2: the axes alone (the gather is a lane-pair swap)
+  constexpr size_t kGatherLds = N == 3 ? (size_t)kBlock * kPieceRow * sizeof(P) + (size_t)kBlock * 16 : 0;
+  P* lds_piece = reinterpret_cast<P*>(smem_raw);
+  lds_u32* lds_off = reinterpret_cast<lds_u32*>(smem_raw + kBlock * kPieceRow * sizeof(P));
+  unsigned char* lds_axes = smem_raw + kGatherLds;
+  LaneAxes<T, N> la;
+  if constexpr (RECT && AXR != 0) {
+    la = load_lane_axes<T, N, AXR>(a.ax);
+  } else if (RECT && a.ax.use_lds) {
+    stage_axes<T, N>(a.ax, lds_axes);
+  }
+  const unsigned char* axis_base = (RECT && AXR == 0 && a.ax.use_lds) ? lds_axes : a.ax.image;
+  const unsigned lane = threadIdx.x;
+  const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(lane >> 6));
+  const size_t nslots = (a.npts + PPL - 1) / PPL;
+  const size_t first = (size_t)blockIdx.x * a.iters * kBlock;
+  typedef T TV __attribute__((ext_vector_type(2)));  // naturally aligned: vector accesses of the wide forms and of `out`
+  constexpr bool kCanWide = (PPL * N) % 2 == 0;
+  constexpr bool kCanLds = N == 3 && sizeof(T) == 8 && PPL == 2;
+  for (unsigned it = 0; it < a.iters; ++it) {
+    // every lane runs every iteration (dead lanes still fetch pieces for their quad / pair)
+    // per lane everything is a 32-bit offset from the iteration's uniform first point p0 (the launcher keeps the strides
+    // below 2^20 elements): uniform bases, one offset register per access
+    const size_t slot0 = first + (size_t)it * kBlock;
+    if (slot0 >= nslots) break;  // block-uniform
+    const size_t p0 = slot0 * PPL;
+    const unsigned left = a.npts - p0 < (size_t)kBlock * PPL ? (unsigned)(a.npts - p0) : (unsigned)kBlock * PPL;  // >= 1
+    // (the lane's offsets are loop invariants: pinned inside the iteration, or they are hoisted and held in registers across it)
+    unsigned lane_in = lane;
+    INTERPN_POINTS_GRAD_PIN(lane_in);
+    const unsigned lp = lane_in * PPL;  // the lane's first point, from p0
+    T xin[PPL][N];
+    bool live[PPL];
+#pragma unroll
+    for (int h = 0; h < PPL; ++h) live[h] = lp + h < left;
+#pragma unroll
+    for (int h = 0; h < PPL; ++h)
+#pragma unroll
+      for (int d = 0; d < N; ++d) xin[h][d] = RECT ? (T)0 : a.start[d];
+    // ---- the coordinate load of k_linear_points
+    bool loaded = false;
+    if constexpr (kCanLds) {
+      const unsigned wl = lane & 63u;
+      const unsigned wave_lp = wave * 64u * PPL;  // the wave's first point, from p0; it has 64 * PPL of them
+      if (a.load == kPointsLoadLds && wave_lp + 64 * PPL <= left) {  // wave-uniform
+        typedef T V16 __attribute__((ext_vector_type(2), aligned(16)));
+        // the wave's quads' rows of the piece area: 16 quads x 4 rows x kPieceRow slots, idle until the gather
+        P* mine = lds_piece + (size_t)wave * 16 * 4 * kPieceRow;
+        static_assert(16 * 4 * kPieceRow >= 64 * PPL * N / 2, "a wave's span fits its part of the piece area");
+        const V16* src = reinterpret_cast<const V16*>(a.pts + (p0 + wave_lp) * N);
+        V16 r[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) r[k] = stream_load(src + k * 64 + wl);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) *reinterpret_cast<V16*>(mine + k * 64 + wl) = r[k];
+        wave_sync();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const P w = mine[wl * 3 + k];
+          xin[(2 * k) / N][(2 * k) % N] = w.x;
+          xin[(2 * k + 1) / N][(2 * k + 1) % N] = w.y;
+        }
+        wave_sync();
+        loaded = true;
+      }
+    }
+    if constexpr (kCanWide) {
+      if (!loaded && a.load != kPointsLoadElem && live[PPL - 1]) {
+        const TV* src = reinterpret_cast<const TV*>(a.pts + p0 * N);
+#pragma unroll
+        for (int k = 0; k < PPL * N / 2; ++k) {
+          const TV w = stream_load(src + (lp * N / 2 + k));
+          xin[(2 * k) / N][(2 * k) % N] = w.x;
+          xin[(2 * k + 1) / N][(2 * k + 1) % N] = w.y;
+        }
+        loaded = true;
+      }
+    }
+    if (!loaded) {  // any stride or alignment, and the batch's ragged tail
+#pragma unroll
+      for (int h = 0; h < PPL; ++h)
+        if (live[h]) {
+          const T* rows = a.pts + p0 * a.stride;
+#pragma unroll
+          for (int d = 0; d < N; ++d) xin[h][d] = stream_load(rows + ((lp + h) * (unsigned)a.stride + d));
+        }
+    }
+    // ---- cell search, gather, value tree and gradient arithmetic of k_linear_grad
+    int cell_r[PPL][N];
+    T x0_r[PPL][N], x1_r[PPL][N];
+    if constexpr (RECT && AXR != 0) lane_axes_locate<T, N, PPL, AXR>(a.ax, la, xin, cell_r, x0_r, x1_r);
+    T resv[PPL], gradv[N][PPL];
+#pragma unroll
+    for (int h = 0; h < PPL; ++h) {
+      T t[N], width[N];
+      int loc[N];
+      bool ok = true;
+#pragma unroll
+      for (int d = 0; d < N; ++d) {
+        const T x = xin[h][d];
+        if (RECT) {
+          T x0, x1;
+          int l;
+          if constexpr (AXR != 0) {
+            l = cell_r[h][d];
+            x0 = x0_r[h][d];
+            x1 = x1_r[h][d];
+          } else {
+            const Axis<T> ax = make_axis<T, N>(a.ax, axis_base, d);
+            l = axis_cell<T>(ax, x, &x0, &x1);  // multilinear/rectilinear.rs:353-370, :310-311
+          }
+          const T step = x1 - x0;
+          t[d] = (x - x0) / step;  // rectilinear.rs:310-313
+          width[d] = step;
+          loc[d] = l;
+        } else {
+          T floc;
+          ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);  // multilinear/regular.rs:415-418
+          const int l = clamp_loc<T>(floc, a.n[d] - 2);             // regular.rs:420-422
+          const T izl = mul_add<FMA>(a.step[d], (T)l, a.start[d]);  // regular.rs:334-337
+          t[d] = (x - izl) / a.step[d];                             // regular.rs:339
+          width[d] = a.step[d];
+          loc[d] = l;
+        }
+      }
+      if (!RECT && !ok && live[h]) atomicMin(a.first_bad, (unsigned long long)(p0 + lp + h));
+      if constexpr (N == 3) {
+        typedef BrickGeom<T, CELL> Geom;
+        const unsigned q = lane & 3;
+        const unsigned quad = lane >> 2;
+        const unsigned bk = (unsigned)loc[2] / (unsigned)Geom::SK;
+        const unsigned kpart = bk * (unsigned)Geom::ELEMS + ((unsigned)loc[2] - bk * (unsigned)Geom::SK);
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+          lds_off[(quad * 4 + p) * 4 + q] = brick_piece<T, SI, SJ, CELL>(a.nbj, a.nbk, loc[0], loc[1], kpart, p >> 1, p & 1);
+        wave_sync();
+        const uint4 toff = *reinterpret_cast<const uint4*>(&lds_off[(quad * 4 + q) * 4]);
+        const Cell<T> c = gather_cell<T>(a.bricks, toff, 0u, lds_piece, quad, q);
+        // value: the tree of k_linear_brick (i first, k last; multilinear/regular.rs:347-403)
+        T r[2];
+#pragma unroll
+        for (int dk = 0; dk < 2; ++dk) {
+          const T c0 = grad_lerp<FMA>(t[0], c.v[0][0][dk], c.v[1][0][dk]);
+          const T c1 = grad_lerp<FMA>(t[0], c.v[0][1][dk], c.v[1][1][dk]);
+          r[dk] = grad_lerp<FMA>(t[1], c0, c1);
+        }
+        resv[h] = grad_lerp<FMA>(t[2], r[0], r[1]);
+        // d/dx0: differences along i, reduced over j then k
+        T s[2];
+#pragma unroll
+        for (int dk = 0; dk < 2; ++dk)
+          s[dk] = grad_lerp<FMA>(t[1], c.v[1][0][dk] - c.v[0][0][dk], c.v[1][1][dk] - c.v[0][1][dk]);
+        gradv[0][h] = grad_lerp<FMA>(t[2], s[0], s[1]) / width[0];
+        // d/dx1: differences along j, reduced over i then k
+#pragma unroll
+        for (int dk = 0; dk < 2; ++dk)
+          s[dk] = grad_lerp<FMA>(t[0], c.v[0][1][dk] - c.v[0][0][dk], c.v[1][1][dk] - c.v[1][0][dk]);
+        gradv[1][h] = grad_lerp<FMA>(t[2], s[0], s[1]) / width[1];
+        // d/dx2: differences along k, reduced over i then j
+#pragma unroll
+        for (int dj = 0; dj < 2; ++dj)
+          s[dj] = grad_lerp<FMA>(t[0], c.v[0][dj][1] - c.v[0][dj][0], c.v[1][dj][1] - c.v[1][dj][0]);
+        gradv[2][h] = grad_lerp<FMA>(t[1], s[0], s[1]) / width[2];
+      } else {
+        // the lane-pair gather of k_linear2_brick: brick (bi = i, bj = j / SJ2), two row pieces per point
+        constexpr unsigned KW2 = 64 / sizeof(T), SJ2 = KW2 - 1, EL2 = 2 * KW2;
+        const unsigned q = lane & 1;
+        const unsigned bj = (unsigned)loc[1] / SJ2;
+        const unsigned mine = ((unsigned)loc[0] * a.nbj + bj) * EL2 + ((unsigned)loc[1] - bj * SJ2);
+        const unsigned theirs = grad_swap1(mine);
+        const unsigned off0 = (q == 0 ? mine : theirs) + q * KW2;
+        const unsigned off1 = (q == 0 ? theirs : mine) + q * KW2;
+        const P p0 = *reinterpret_cast<const P*>(a.bricks + off0);
+        const P p1 = *reinterpret_cast<const P*>(a.bricks + off1);
+        const P keep = q == 0 ? p0 : p1;
+        const P send = q == 0 ? p1 : p0;
+        P recv;
+        recv.x = grad_swap1(send.x);
+        recv.y = grad_swap1(send.y);
+        const P row0 = q == 0 ? keep : recv;  // v(i, j), v(i, j+1)
+        const P row1 = q == 0 ? recv : keep;  // row i+1
+        const T c0 = grad_lerp<FMA>(t[0], row0.x, row1.x);
+        const T c1 = grad_lerp<FMA>(t[0], row0.y, row1.y);
+        resv[h] = grad_lerp<FMA>(t[1], c0, c1);
+        gradv[0][h] = grad_lerp<FMA>(t[1], row1.x - row0.x, row1.y - row0.y) / width[0];
+        gradv[1][h] = grad_lerp<FMA>(t[0], row0.y - row0.x, row1.y - row1.x) / width[1];
+      }
+      if (h + 1 < PPL) {  // this point's results are complete here: they are not left to be computed behind the next gather
+        INTERPN_POINTS_GRAD_PIN(resv[h]);
+#pragma unroll
+        for (int d = 0; d < N; ++d) INTERPN_POINTS_GRAD_PIN(gradv[d][h]);
+      }
+    }
+    // ---- the value store of k_linear_points
+    unsigned lane_out = lane;
+    INTERPN_POINTS_GRAD_PIN(lane_out);
+    const unsigned lq = lane_out * PPL;  // lp again, computed here
+    if constexpr (PPL >= 2) {
+      if (live[PPL - 1]) {
+        TV v;
+#pragma unroll
+        for (int h = 0; h < PPL; ++h) v[h] = resv[h];
+        stream_store(reinterpret_cast<TV*>(a.out + p0) + lane_out, v);
+      } else {
+#pragma unroll
+        for (int h = 0; h < PPL; ++h)
+          if (live[h]) stream_store(a.out + p0 + (lq + h), resv[h]);
+      }
+    } else if (live[0]) {
+      stream_store(a.out + p0 + lq, resv[0]);
+    }
+    // ---- the gradient-row store: element e of the lane's PPL * N is component e % N of its point e / N
+    bool stored = false;
+    if constexpr (kCanLds) {
+      const unsigned wl = lane & 63u;
+      const unsigned wave_lp = wave * 64u * PPL;
+      if (a.store == kPointsStoreLds && wave_lp + 64 * PPL <= left) {  // wave-uniform
+        typedef T V16 __attribute__((ext_vector_type(2), aligned(16)));
+        P* mine = lds_piece + (size_t)wave * 16 * 4 * kPieceRow;  // idle: the last gather has read its pieces back
+        wave_sync();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          P w;
+          w.x = gradv[(2 * k) % N][(2 * k) / N];
+          w.y = gradv[(2 * k + 1) % N][(2 * k + 1) / N];
+          mine[wl * 3 + k] = w;
+        }
+        wave_sync();
+        V16 r[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) r[k] = *reinterpret_cast<const V16*>(mine + k * 64 + wl);
+        V16* dst = reinterpret_cast<V16*>(a.grad + (p0 + wave_lp) * N);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) stream_store(dst + k * 64 + wl, r[k]);
+        wave_sync();  // the next iteration's coordinate load or gather reuses the area
+        stored = true;
+      }
+    }
+    if constexpr (kCanWide) {
+      if (!stored && a.store != kPointsStoreElem && live[PPL - 1]) {
+        TV* dst = reinterpret_cast<TV*>(a.grad + p0 * N);
+#pragma unroll
+        for (int k = 0; k < PPL * N / 2; ++k) {
+          TV w;
+          w.x = gradv[(2 * k) % N][(2 * k) / N];
+          w.y = gradv[(2 * k + 1) % N][(2 * k + 1) / N];
+          stream_store(dst + (lq * N / 2 + k), w);
+        }
+        stored = true;
+      }
+    }
+    if (!stored) {  // any stride or alignment, and the batch's ragged tail
+#pragma unroll
+      for (int h = 0; h < PPL; ++h)
+        if (live[h]) {
+          T* rows = a.grad + p0 * a.gstride;
+#pragma unroll
+          for (int d = 0; d < N; ++d) stream_store(rows + ((lq + h) * (unsigned)a.gstride + d), gradv[d][h]);
+        }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T, int N>
+struct CubicPointsGradArgs {
+  const T* bricks;
+  unsigned table_bytes;  // < 4 GiB
+  const T* pts;
+  size_t stride;
+  T* out;
+  T* grad;
+  size_t gstride;
+  unsigned long long* first_bad;
+  size_t npts;
+  int vec2_load;   // N == 2: stride == 2 and an aligned base: one two-element load per point
+  int vec2_store;  // N == 2: gstride == 2 and an aligned base: one two-element store per point
+  T start[N];
+  T step[N];
+  int n[N];
+  AxisArgs<T, N> ax;
+  unsigned plane_stride[N];  // d >= 2: table elements per unit index of dim d
+  unsigned nbj;
+  int linearize;
+};
+
+template <typename T, int N, bool RECT, bool FMA, int SI, int SJ>
+__global__ void __launch_bounds__(kBlock) k_cubic_points_grad(const CubicPointsGradArgs<T, N> a) {
+  static_assert(N == 2 || N == 3, "fused point-major multicubic gradient kernel: N = 2, 3");
+  typedef typename CubicDimSel<T, RECT>::type DimT;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  typedef T __attribute__((may_alias)) lds_T;
+  lds_T* lds_data = reinterpret_cast<lds_T*>(smem_raw);
+  lds_u32* lds_off = reinterpret_cast<lds_u32*>(smem_raw);
+  constexpr bool DMA = cubic_dma<T, SI, SJ>();
+  constexpr size_t kRegion = cubic_lds_region<T, SI, SJ>();
+  constexpr int NP = N == 2 ? 1 : 4;  // planes of a point
+  typedef T TV __attribute__((ext_vector_type(2)));
+  unsigned char* lds_axes = smem_raw + kRegion;
+  if (RECT && a.ax.use_lds) stage_axes<T, N>(a.ax, lds_axes);
+  const unsigned char* axis_base = (RECT && a.ax.use_lds) ? lds_axes : a.ax.image;
+  const unsigned lane = threadIdx.x;
+  const unsigned me = lane & 15;
+  const unsigned group = lane >> 4;
+  const unsigned goff = group * (unsigned)(16 * kCubRow * sizeof(T) / 4);
+  const __amdgpu_buffer_rsrc_t rsrc = table_rsrc(a.bricks, a.table_bytes);
+  const unsigned lds_wave = (unsigned)__builtin_amdgcn_readfirstlane(
+      (int)((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_raw + (lane >> 6) * cubic_dma_image<T>()));
+  const size_t nthreads = (size_t)gridDim.x * kBlock;
+  const size_t niter = (a.npts + nthreads - 1) / nthreads;
+  for (size_t it = 0; it < niter; ++it) {
+    // every lane runs every iteration: dead lanes take part in the gathers' exchanges with the offsets of a valid point
+    const size_t i0 = it * nthreads + (size_t)blockIdx.x * kBlock + lane;
+    const bool live = i0 < a.npts;
+    // the point's row
+    T xin[N];
+#pragma unroll
+    for (int d = 0; d < N; ++d) xin[d] = RECT ? (T)0 : a.start[d];
+    if (live) {
+      bool loaded = false;
+      if constexpr (N == 2) {
+        if (a.vec2_load) {
+          const TV w = stream_load(reinterpret_cast<const TV*>(a.pts) + i0);
+          xin[0] = w.x;
+          xin[1] = w.y;
+          loaded = true;
+        }
+      }
+      if (!loaded) {
+        const T* row = a.pts + i0 * a.stride;
+#pragma unroll
+        for (int d = 0; d < N; ++d) xin[d] = stream_load(row + d);
+      }
+    }
+    DimT dim[N];
+    int loc[N];
+    T width[N];
+    bool ok = true;
+#pragma unroll
+    for (int d = 0; d < N; ++d) {
+      const T x = xin[d];
+      if constexpr (RECT) {
+        const Axis<T> ax = make_axis<T, N>(a.ax, axis_base, d);
+        loc[d] = cubic_rect_locate<T>(ax, x, a.linearize, /*fma_linear=*/false, dim[d]);  // multicubic/rectilinear.rs:366-408
+        width[d] = cubic_rect_width<T>(ax.g, loc[d], dim[d].sat);
+      } else {
+        T floc;
+        ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);   // multicubic/regular.rs:435-438
+        ok &= floc != (T)-9223372036854775808.0;                  // `- 1` would overflow isize
+        const T nn = (T)a.n[d];
+        const int l = clamp_loc<T>(floc - (T)1, a.n[d] - 4);      // regular.rs:440-442
+        int sat;
+        bool outside;
+        if (floc < (T)0) { sat = kSatLow; outside = true; }       // regular.rs:445-466 on floc = iloc + 1
+        else if (floc == (T)0) { sat = kSatLow; outside = false; }
+        else if (floc > nn - (T)2) { sat = kSatHigh; outside = true; }
+        else if (floc == nn - (T)2) { sat = kSatHigh; outside = false; }
+        else { sat = kSatNone; outside = false; }
+        const T index_one_loc = mul_add<false>(a.step[d], (T)(l + 1), a.start[d]);  // regular.rs:356-360, never fused
+        const T t = (x - index_one_loc) / a.step[d];
+        dim[d].sat = sat;
+        dim[d].linear = (outside && a.linearize) ? 1 : 0;
+        dim[d].tt = sat == kSatLow ? -t : (sat == kSatHigh ? t - (T)1 : t);
+        loc[d] = l;
+        width[d] = a.step[d];
+      }
+    }
+    if (!RECT && !ok && live) atomicMin(a.first_bad, (unsigned long long)i0);
+    unsigned pbase = 0;  // element offsets here, bytes in LDS
+    if constexpr (N == 3) pbase = (unsigned)loc[2] * a.plane_stride[2];
+    unsigned toff[16];
+    if constexpr (DMA) {
+      constexpr unsigned PP = (unsigned)sizeof(T);
+      const unsigned wl = lane & 63u;
+      const unsigned tb = (pbase + (unsigned)(loc[0] * (int)a.nbj + loc[1]) * 16u) * (unsigned)sizeof(T);
+#pragma unroll
+      for (int q = 0; q < (int)PP; ++q) {
+        const unsigned p = ((unsigned)q * 64u + wl) / PP;
+        const unsigned c = ((wl & (PP - 1u)) - cubic_dma_rot<T>(p)) & (PP - 1u);
+        toff[q] = (unsigned)__shfl((int)tb, (int)p) + c * 16u;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        int bi, oi, bj, oj;
+        tile_coord<SI>(loc[0], e >> 2, &bi, &oi);
+        tile_coord<SJ>(loc[1], e & 3, &bj, &oj);
+        lds_off[goff + e * kCubRow + me] = (pbase + ((unsigned)(bi * (int)a.nbj + bj) * 16u) + (unsigned)(oi * 4 + oj)) * (unsigned)sizeof(T);
+      }
+      wave_sync();
+#pragma unroll
+      for (int r = 0; r < 16; ++r) toff[r] = lds_off[goff + me * kCubRow + r];
+      wave_sync();
+    }
+    auto delta_of = [&](int k) -> unsigned {  // byte offset of plane k along dim 2
+      if constexpr (N == 3) return (unsigned)k * a.plane_stride[2] * (unsigned)sizeof(T);
+      else return 0u;
+    };
+    // per plane: the value, d/dx0 and d/dx1 after dims 0 and 1; planes in the reference's order (dim 2 ascending)
+    T sv[NP], s0[NP], s1[NP];
+    if constexpr (DMA) dma_issue_plane<T>(rsrc, toff, delta_of(0), lds_wave);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      T v[16];
+      if constexpr (DMA) {
+        dma_take_tile<T>(lds_wave, lane & 63u, v);
+        if (k + 1 < NP) dma_issue_plane<T>(rsrc, toff, delta_of(k + 1), lds_wave);
+      } else {
+        grad_gather_tile<T>(rsrc, toff, delta_of(k), lds_data, group, me, v);
+      }
+      grad_reduce_tile<T, RECT, FMA>(v, dim, sv[k], s0[k], s1[k]);
+    }
+    T res, g[N];
+    if constexpr (N == 2) {
+      res = sv[0];
+      g[0] = s0[0];
+      g[1] = s1[0];
+    } else {
+      cubic_node_vd<RECT, FMA, T>(sv[0], sv[1], sv[2], sv[3], dim[2], res, g[2]);
+      g[0] = cubic_node_sel<RECT, FMA, T>(s0[0], s0[1], s0[2], s0[3], dim[2]);
+      g[1] = cubic_node_sel<RECT, FMA, T>(s1[0], s1[1], s1[2], s1[3], dim[2]);
+    }
+    if (live) {
+      stream_store(a.out + i0, res);
+      T comp[N];
+#pragma unroll
+      for (int d = 0; d < N; ++d) {
+        const T s = dim[d].sat == kSatLow ? -g[d] : g[d];
+        comp[d] = s / width[d];
+      }
+      bool stored = false;
+      if constexpr (N == 2) {
+        if (a.vec2_store) {
+          TV w;
+          w.x = comp[0];
+          w.y = comp[1];
+          stream_store(reinterpret_cast<TV*>(a.grad) + i0, w);
+          stored = true;
+        }
+      }
+      if (!stored) {
+        T* row = a.grad + i0 * a.gstride;
+#pragma unroll
+        for (int d = 0; d < N; ++d) stream_store(row + d, comp[d]);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+struct JoinArgs {
+  const T* src[kMaxDims];
+  T* grad;
+  size_t gstride;
+  size_t count;
+  int ndims;
+};
+
+// One workgroup per kBlock points: their gradient rows are kBlock * gstride consecutive elements.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_join_grad(const JoinArgs<T> a) {
+  __shared__ T tile[kMaxDims][kBlock + 1];
+  const size_t p0 = (size_t)blockIdx.x * kBlock;
+  const size_t here = a.count - p0 < (size_t)kBlock ? a.count - p0 : (size_t)kBlock;
+  T* rows = a.grad + p0 * a.gstride;
+  if (a.gstride > kSplitTileStride) {  // rows of long records: a lane per point, nothing to coalesce (launch-uniform)
+    if (threadIdx.x < here)
+      for (int d = 0; d < a.ndims; ++d) stream_store(rows + threadIdx.x * a.gstride + d, a.src[d][p0 + threadIdx.x]);
+    return;
+  }
+  if (threadIdx.x < here)
+    for (int d = 0; d < a.ndims; ++d) tile[d][threadIdx.x] = a.src[d][p0 + threadIdx.x];
+  __syncthreads();
+  const unsigned stride = (unsigned)a.gstride;
+  const unsigned span = (unsigned)here * stride;
+  for (unsigned e = threadIdx.x; e < span; e += kBlock) {
+    const unsigned p = e / stride;
+    const unsigned d = e - p * stride;
+    // elements d >= ndims of a row are somebody else's (the last row's may not even exist): never written
+    if (d < (unsigned)a.ndims) stream_store(rows + e, tile[d][p]);
+  }
+}
+
+}  // namespace interpn

@@ -447,6 +447,115 @@ class Interpolator:
         self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
         return out
 
+    # -- point-major value and gradient (positions (n, N) in, gradient (n, N) out) -----------------
+    def reserve_points_grad(self, npoints: int, nstreams: int = 1) -> None:
+        """`reserve_points` for `eval_points_grad_tensors`: a slice of its split path needs N coordinate and N component
+        arrays (`interpn_hip_reserve_points_grad`).  The fused kernels (multilinear and multicubic N = 2, 3) need none."""
+        _lib.raise_for_status(_lib.load().interpn_hip_reserve_points_grad(self._h, int(npoints), int(nstreams)))
+
+    def eval_points_grad_host(self, pts: np.ndarray, out: np.ndarray = None, grad: np.ndarray = None):
+        """Value and gradient on a host array of shape `(n, N)` whose rows are points (synchronous;
+        `interpn_hip_eval_points_grad_host`): returns `(out, grad)` of shapes `(n,)` and `(n, N)` with the bits of
+        `eval_grad_host` (multilinear handles) or `eval_cubic_grad_host` (multicubic handles) on the columns `pts[:, d]`,
+        `grad[i, d]` being the derivative with respect to coordinate d at point i.  `pts` as for `eval_points_host`; a
+        caller's `grad` may be a row-strided view such as `g[:, :3]` of an `(n, 4)` array, whose other columns are left
+        alone.  On "Unrepresentable coordinate value" exactly the entries in front of the failing point have been written."""
+        if not isinstance(pts, np.ndarray):
+            raise TypeError(f"argument 'pts': expected a numpy array, got {type(pts).__name__}")
+        if pts.dtype != self.dtype:
+            raise TypeError(f"argument 'pts': expected dtype {self.dtype.name}, got {pts.dtype.name}")
+        if pts.ndim != 2:
+            raise TypeError(f"argument 'pts': expected a 2-D array of shape (n, {self._ndims}), got {pts.ndim} dimension(s)")
+        n, width = pts.shape
+        if width != self._ndims:
+            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        item = pts.itemsize
+
+        def row_stride(name, a):
+            stride = self._ndims
+            if n > 1 or width > 1:
+                if width > 1 and a.strides[1] != item:
+                    raise ValueError(f"argument '{name}': every row must be contiguous")
+                if n > 1:
+                    if a.strides[0] % item or a.strides[0] < self._ndims * item:
+                        raise ValueError(f"argument '{name}': the row stride must be a whole number of elements, at least {self._ndims}")
+                    stride = a.strides[0] // item
+            return stride
+
+        stride = row_stride("pts", pts)
+        if out is None:
+            out = np.zeros(n, dtype=self.dtype)
+        out = _check_arr("out", out, self.dtype, writable=True)
+        if out.size != n:
+            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        if grad is None:
+            grad = np.zeros((n, width), dtype=self.dtype)
+        if not isinstance(grad, np.ndarray):
+            raise TypeError(f"argument 'grad': expected a numpy array, got {type(grad).__name__}")
+        if grad.dtype != self.dtype:
+            raise TypeError(f"argument 'grad': expected dtype {self.dtype.name}, got {grad.dtype.name}")
+        if grad.shape != (n, width):
+            raise ValueError(f"grad: expected shape {(n, width)}, got {grad.shape}")
+        if not grad.flags.writeable:
+            raise ValueError("argument 'grad': array is read-only")
+        gstride = row_stride("grad", grad)
+        st = _lib.load().interpn_hip_eval_points_grad_host(self._h, c_void_p(pts.ctypes.data), stride, n, out.ctypes.data_as(c_void_p),
+                                                           c_void_p(grad.ctypes.data), gstride)
+        _lib.raise_for_status(st)
+        return out, grad
+
+    def eval_points_grad_tensors(self, pts, out=None, grad=None, stream=None, no_alloc: bool = False):
+        """The same on a torch CUDA tensor of shape `(n, N)` with `stride(1) == 1` and `stride(0) >= N`, without
+        `pts.T.contiguous()` in front and `grad.T.contiguous()` behind (`interpn_hip_eval_points_grad_device`): returns
+        `(out, grad)` of shapes `(n,)` and `(n, N)`.  A caller's `grad` may be a row-strided view (`stride(1) == 1`,
+        `stride(0) >= N`) that does not overlap `pts`.  Asynchronous like `eval_tensors`; multilinear and multicubic
+        N = 2, 3 are one kernel and capturable.  `last_points_path()` says which path ran; `finish()` synchronises and
+        surfaces "Unrepresentable coordinate value"."""
+        import torch
+
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        nd = self._ndims
+        what = f"pts: expected a 2-D {want} CUDA tensor of shape (n, {nd}) with stride(1) == 1 and stride(0) >= {nd}"
+        if not (hasattr(pts, "is_cuda") and pts.is_cuda and pts.dim() == 2 and pts.dtype == want):
+            raise TypeError(what)
+        n, width = int(pts.shape[0]), int(pts.shape[1])
+        if (width > 1 and pts.stride(1) != 1) or (n > 1 and pts.stride(0) < width):
+            raise TypeError(what)
+        if width != nd:
+            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        self._check_same_device("pts", pts)
+        stride = int(pts.stride(0)) if n > 1 else nd
+        dev = torch.device("cuda", self.device())
+        if out is None:
+            out = torch.empty(n, dtype=want, device=dev)
+        elif not (out.is_cuda and out.is_contiguous() and out.dim() == 1 and out.dtype == want):
+            raise TypeError(f"out: expected a contiguous 1-D {want} CUDA tensor")
+        elif out.numel() != n:
+            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        else:
+            self._check_same_device("out", out)
+        gwhat = f"grad: expected a 2-D {want} CUDA tensor of shape ({n}, {nd}) with stride(1) == 1 and stride(0) >= {nd}"
+        if grad is None:
+            grad = torch.empty((n, nd), dtype=want, device=dev)
+        elif not (hasattr(grad, "is_cuda") and grad.is_cuda and grad.dim() == 2 and grad.dtype == want):
+            raise TypeError(gwhat)
+        elif tuple(grad.shape) != (n, nd):
+            raise ValueError(f"grad: expected shape {(n, nd)}, got {tuple(grad.shape)}")
+        elif (nd > 1 and grad.stride(1) != 1) or (n > 1 and grad.stride(0) < nd):
+            raise TypeError(gwhat)
+        else:
+            self._check_same_device("grad", grad)
+        gstride = int(grad.stride(0)) if n > 1 else nd
+        owner = torch.cuda.current_stream(self.device()) if stream is None else stream
+        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        path = ctypes.c_int(0)
+        st = _lib.load().interpn_hip_eval_points_grad_device(self._h, c_void_p(pts.data_ptr()), stride, n, c_void_p(out.data_ptr()),
+                                                             c_void_p(grad.data_ptr()), gstride, c_void_p(int(raw)),
+                                                             _lib.EVAL_NO_ALLOC if no_alloc else 0, ctypes.byref(path))
+        _lib.raise_for_status(st)
+        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        return out, grad
+
     # -- lattice evaluation (points = tensor product of one coordinate vector per axis) ----
     @property
     def last_lattice_path(self):
