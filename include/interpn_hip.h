@@ -418,9 +418,12 @@ int interpn_hip_eval_device_ex(interpn_hip_interp* h, const void* const* obs, si
 
 /* Pre-allocate what device-pointer evaluations of up to `npoints` points on up to `nstreams`
  * concurrent streams need (the sorted path's scratch blocks; nothing for handles that never
- * sort).  Synchronous; may be called again with larger numbers.  Per-handle counters readable
- * with interpn_hip_get_option: "evals_binned", "evals_in_place", "scratch_allocs",
- * "scratch_bytes". */
+ * sort).  Synchronous; may be called again with larger numbers.  It counts every scratch block of
+ * the handle that is large enough, whoever made it: behind interpn_hip_reserve_points / _lattice
+ * ask for 2 * nstreams, a slice holds one block while its evaluation takes another.  A handle
+ * owns at most 4 blocks and `nstreams` is clamped to 4, so both levels can be reserved for two
+ * streams at most.  Per-handle counters readable with interpn_hip_get_option: "evals_binned",
+ * "evals_in_place", "evals_sweep", "scratch_allocs", "scratch_bytes". */
 int interpn_hip_reserve(interpn_hip_interp* h, size_t npoints, int nstreams);
 
 /* Measurement aid (bench.py): with option "stage_timing" = 1 a sorted (binned) single-slice
@@ -582,6 +585,8 @@ int interpn_hip_fields_device(const interpn_hip_fields* fields);
  * after a fused one, the first field's kernel after a per-field one. */
 int interpn_hip_fields_kernel_name(const interpn_hip_fields* fields, char* buf, size_t buflen);
 int interpn_hip_fields_set_option(interpn_hip_fields* fields, const char* name, long long value);
+/* "fused", "fused_table_bytes", "nfields", "last_path": the set's own; "evals_binned", "evals_in_place", "evals_sweep":
+ * summed over the K handles; every other name: the first handle's (interpn_hip_get_option). */
 int interpn_hip_fields_get_option(const interpn_hip_fields* fields, const char* name, long long* value);
 /* The fused table of `nfields` fields of `elem_size` (4, 8) bytes on a grid of `dims` (ndims = 2, 3; every axis >= 2):
  * P, ceil(nfields / P) and the table's size.  Needs no device.  INTERPN_HIP_ERR_INVALID_ARGUMENT for anything else. */
@@ -639,8 +644,9 @@ int interpn_hip_eval_lattice_device(interpn_hip_interp* h, const void* const* ax
 int interpn_hip_eval_lattice_host(interpn_hip_interp* h, const void* const* axes, const size_t* axis_lens, size_t naxes,
                                   void* out, uint64_t* first_bad_index);
 /* Scratch blocks for lattices of up to these axis lengths on up to `nstreams` concurrent streams, whichever path the
- * options choose at evaluation time.  Synchronous.  (An expanded slice that the handle would sort or sweep takes a
- * second block: interpn_hip_reserve; without one it is evaluated in place.) */
+ * options choose at evaluation time.  Synchronous.  An expanded slice that the handle would sort or sweep takes a
+ * second block while it holds the first; without one it is evaluated in place.  interpn_hip_reserve counts every block
+ * that is large enough, these among them: call it with 2 * nstreams behind this call (see interpn_hip_reserve_points). */
 int interpn_hip_reserve_lattice(interpn_hip_interp* h, const size_t* axis_lens, size_t naxes, int nstreams);
 /* Which path a lattice of `axis_lens` on a grid of `dims` takes in automatic mode on an MI355X, the fused workgroup's
  * LDS bytes (0 when expanded) and the overflow-checked point count.  Needs no device; honours the INTERPN_HIP_*
@@ -694,7 +700,12 @@ int interpn_hip_eval_points_device(interpn_hip_interp* h, const void* pts, size_
  * of `out` is left as it was.  Shares the sticky status word with the device form: finish device evaluations first. */
 int interpn_hip_eval_points_host(interpn_hip_interp* h, const void* pts, size_t point_stride, size_t npoints, void* out);
 /* Scratch blocks for split-path evaluations of up to `npoints` points on up to `nstreams` concurrent streams.
- * Synchronous.  (A slice that the handle would sort or sweep takes a second block: interpn_hip_reserve.) */
+ * Synchronous.  A slice that the handle would sort or sweep takes a second block while it holds the first, and this call
+ * sizes the first only.  interpn_hip_reserve counts EVERY block of the handle that is large enough, the slices' among them:
+ * call it with the slice's point count and 2 * nstreams (one stream: nstreams + 1) behind this call.  A handle owns at
+ * most 4 blocks and both calls clamp `nstreams` to 4: both levels can be reserved for two streams at most; with three
+ * or four, some slices find no second block.  With one block per stream the slices are evaluated in place, under
+ * INTERPN_HIP_EVAL_NO_ALLOC and under capture (which never sorts or sweeps); the results are the same bits. */
 int interpn_hip_reserve_points(interpn_hip_interp* h, size_t npoints, int nstreams);
 
 /* ------------------------------------------------------------------------------------------

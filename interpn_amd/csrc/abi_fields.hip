@@ -375,6 +375,17 @@ int interpn_hip_fields_get_option(const interpn_hip_fields* s, const char* name,
   if (!strcmp(name, "fused_table_bytes")) { *value = s->table ? (long long)s->table_bytes : 0; return INTERPN_HIP_OK; }
   if (!strcmp(name, "nfields")) { *value = (long long)s->nfields; return INTERPN_HIP_OK; }
   if (!strcmp(name, "last_path")) { *value = s->last_path; return INTERPN_HIP_OK; }
+  if (!strncmp(name, "evals_", 6)) {  // the per-field path evaluates through every handle: their counters, summed
+    long long sum = 0;
+    for (const interpn_hip_interp* h : s->sub) {
+      long long v = 0;
+      const int st = interpn_hip_get_option(h, name, &v);
+      if (st) return st;
+      sum += v;
+    }
+    *value = sum;
+    return INTERPN_HIP_OK;
+  }
   return interpn_hip_get_option(s->sub[0], name, value);
 }
 

@@ -14,14 +14,16 @@ from tests.helpers import run_hip_raw, run_oracle, synthetic_case
 KNOBS = ("INTERPN_HIP_BRICKS", "INTERPN_HIP_PPL", "INTERPN_HIP_FORCE_GENERIC", "INTERPN_HIP_GENERIC_RUNTIME",
          "INTERPN_HIP_HOST_CHUNK", "INTERPN_HIP_ITERS_PER_BLOCK", "INTERPN_HIP_AXIS_REGS", "INTERPN_HIP_GENERIC_VEC", "INTERPN_HIP_PERSISTENT",
          "INTERPN_HIP_BINNED", "INTERPN_HIP_DEAL", "INTERPN_HIP_COLUMN", "INTERPN_HIP_COLUMN_THREADS", "INTERPN_HIP_COLUMN_PART",
-         "INTERPN_HIP_COLUMN_GROUPS", "INTERPN_HIP_COLUMN_CPP", "INTERPN_HIP_COLUMN_COEF", "INTERPN_HIP_COLUMN_PAD", "INTERPN_HIP_COLUMN_TAIL", "INTERPN_HIP_COLUMN_KEYS", "INTERPN_HIP_SCATTER_STAGED", "INTERPN_HIP_BIN_SCRAMBLE", "INTERPN_HIP_AXIS_RECORDS", "INTERPN_HIP_BIN_SLICE_LOG2", "INTERPN_HIP_SWEEP", "INTERPN_HIP_SWEEP_PERIOD", "INTERPN_HIP_CUBIC_RECORDS", "INTERPN_HIP_SWEEP_PROBE", "INTERPN_HIP_GATED_ITERS", "INTERPN_HIP_SWEEP_LAYOUT")
+         "INTERPN_HIP_COLUMN_GROUPS", "INTERPN_HIP_COLUMN_CPP", "INTERPN_HIP_COLUMN_COEF", "INTERPN_HIP_COLUMN_PAD", "INTERPN_HIP_COLUMN_TAIL", "INTERPN_HIP_COLUMN_KEYS", "INTERPN_HIP_SCATTER_STAGED", "INTERPN_HIP_BIN_SCRAMBLE", "INTERPN_HIP_AXIS_RECORDS", "INTERPN_HIP_BIN_SLICE_LOG2", "INTERPN_HIP_SWEEP", "INTERPN_HIP_SWEEP_PERIOD", "INTERPN_HIP_CUBIC_RECORDS", "INTERPN_HIP_SWEEP_PROBE", "INTERPN_HIP_GATED_ITERS", "INTERPN_HIP_SWEEP_LAYOUT",
+         "INTERPN_HIP_POINTS_PATH", "INTERPN_HIP_POINTS_SLICE", "INTERPN_HIP_LATTICE")
 LAYOUTS_LIN = [None, "off", "11", "12", "22", "c4"]
 LAYOUTS_CUB = [None, "off", "44", "24", "22", "14", "11"]
 
 
 def run_device(case, rng, dtype, fma=None):
     """The persistent-handle device entry point on torch tensors whose first element sits at a
-    random element offset (exercises the aligned-vector and the scalar stream paths)."""
+    random element offset (exercises the aligned-vector and the scalar stream paths); a third of the
+    cases pass the points interleaved through `eval_points_tensors` instead."""
     import torch
 
     import interpn_amd
@@ -45,7 +47,18 @@ def run_device(case, rng, dtype, fma=None):
         off = int(rng.choice([0, 2, 0, 2, 3])) if sweep else int(rng.integers(0, 4))
         out_full = torch.full((nobs + off,), -777.0, dtype=obs_t[0].dtype, device="cuda")
         out_t = out_full[off:]
-        it.eval_tensors(obs_t, out_t)
+        if rng.random() < 0.35:
+            # the same points as ONE (n, N) tensor (rows of N or N + 1 elements) through the point-major entry point: mostly the
+            # split path in small slices, so that every knob above also runs behind the slices; against the same oracle result
+            nd = len(case.obs)
+            it.set_option("points_path", int(rng.choice([2, 2, 0])))
+            it.set_option("points_slice", int(rng.choice([256, 4096, 65536])))
+            rows = torch.full((nobs, nd + int(rng.integers(0, 2))), 1e30, dtype=out_t.dtype, device="cuda")
+            for d, t in enumerate(obs_t):
+                rows[:, d] = t
+            it.eval_points_tensors(rows[:, :nd], out_t)
+        else:
+            it.eval_tensors(obs_t, out_t)
         err, first_bad = None, None
         try:
             it.finish()
