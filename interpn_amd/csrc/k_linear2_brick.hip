@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "lane_axes.h"
+#include "linear_cell.h"
 #include "sweep_rounds.h"
 #include "rect_args.h"
 
@@ -37,17 +38,6 @@ struct Brick2Args {
   unsigned nbj;
   const unsigned* gate;  // gated launch (GridDesc::launch_gate): null, or a word that must be non-zero for this launch to do anything
 };
-
-// swap with the neighbouring lane (lane ^ 1): quad_perm [1,0,3,2]
-__device__ __forceinline__ unsigned dpp_swap1(unsigned v) {
-  return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
-}
-__device__ __forceinline__ float dpp_swap1(float v) { return __uint_as_float(dpp_swap1(__float_as_uint(v))); }
-__device__ __forceinline__ double dpp_swap1(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = dpp_swap1((unsigned)b), hi = dpp_swap1((unsigned)(b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 // AXR != 0 (rectilinear, both axes <= 64 coordinates): axes in lanes, see lane_axes.h.
 // PPL = 2: a lane owns two consecutive points, coordinates and results move as 2*sizeof(T)-byte
@@ -130,7 +120,7 @@ __global__ void __launch_bounds__(kBlock) k_linear2_brick(const Brick2Args<T> a)
       // brick (bi = i, bj = j / SJ); my point's pair starts at column j - bj*SJ of both rows
       const unsigned bj = (unsigned)loc[1] / (unsigned)SJ;
       const unsigned mine = ((unsigned)loc[0] * a.nbj + bj) * (unsigned)Brick2Geom<T>::ELEMS + ((unsigned)loc[1] - bj * (unsigned)SJ);
-      const unsigned theirs = dpp_swap1(mine);
+      const unsigned theirs = lane_swap1(mine);
       // instruction r fetches point r of the pair (r = 0: even lane's point, r = 1: odd lane's)
       const unsigned off0 = (q == 0 ? mine : theirs) + q * (unsigned)KW;
       const unsigned off1 = (q == 0 ? theirs : mine) + q * (unsigned)KW;
@@ -140,8 +130,8 @@ __global__ void __launch_bounds__(kBlock) k_linear2_brick(const Brick2Args<T> a)
       const P keep = q == 0 ? p0 : p1;
       const P send = q == 0 ? p1 : p0;
       P recv;
-      recv.x = dpp_swap1(send.x);
-      recv.y = dpp_swap1(send.y);
+      recv.x = lane_swap1(send.x);
+      recv.y = lane_swap1(send.y);
       const P row0 = q == 0 ? keep : recv;  // row i   : v(i, j), v(i, j+1)
       const P row1 = q == 0 ? recv : keep;  // row i+1
       // reference tree: dim 0 first for each j, then dim 1 (multilinear/regular.rs:347-403)
@@ -216,7 +206,7 @@ __global__ void __launch_bounds__(THREADS) k_linear2_sweep(const Linear2SweepArg
     // the rows of k_linear2_brick: brick (bi = i, bj = j / SJ), lane pairs fetch the two row pieces of one point per load
     const unsigned bj = (unsigned)loc[1] / (unsigned)SJ;
     const unsigned mine_e = ((unsigned)loc[0] * s.nbj + bj) * (unsigned)Brick2Geom<T>::ELEMS + ((unsigned)loc[1] - bj * (unsigned)SJ);
-    const unsigned theirs = dpp_swap1(mine_e);
+    const unsigned theirs = lane_swap1(mine_e);
     const unsigned off0 = (q == 0 ? mine_e : theirs) + q * (unsigned)KW;
     const unsigned off1 = (q == 0 ? theirs : mine_e) + q * (unsigned)KW;
     const P p0 = *reinterpret_cast<const P*>(s.bricks + off0);
@@ -224,8 +214,8 @@ __global__ void __launch_bounds__(THREADS) k_linear2_sweep(const Linear2SweepArg
     const P keep = q == 0 ? p0 : p1;
     const P send = q == 0 ? p1 : p0;
     P recv;
-    recv.x = dpp_swap1(send.x);
-    recv.y = dpp_swap1(send.y);
+    recv.x = lane_swap1(send.x);
+    recv.y = lane_swap1(send.y);
     const P row0 = q == 0 ? keep : recv;
     const P row1 = q == 0 ? recv : keep;
     const T c0 = mul_add<FMA>(t[0], row1.x - row0.x, row0.x);  // multilinear/regular.rs:347-403

@@ -1,8 +1,9 @@
 // Host side of the point-major value-and-gradient evaluation (points_grad.h): whether a fused kernel takes a handle,
-// their launchers (the dispatch of k_linear_points.hip and k_cubic_grad.hip), the load and store forms, and the launcher
-// of the split path's interleaving kernel.
+// their launchers (the multilinear one through linear_cell_launch.h, the multicubic one with the dispatch of
+// k_cubic_grad.hip), the gradient-row store form, and the launcher of the split path's interleaving kernel.
 #include <cstdlib>
 
+#include "linear_cell_launch.h"
 #include "points_grad.h"
 
 namespace interpn {
@@ -16,91 +17,24 @@ bool points_grad_fused_applies(const GridDesc& g, size_t stride, size_t gstride)
   return g.method == kCubic && g.bricks && !g.cfg.force_generic && (g.ndims == 2 || g.ndims == 3);
 }
 
-template <typename T, int N, bool RECT, bool FMA, int PPL, int AXR>
-static hipError_t pg_launch_steps(const GridDesc& g, const PointsGradArgs<T, N>& a, size_t lds, unsigned blocks, hipStream_t stream) {
-#define PG_GO(SI, SJ, CELL)                                                                                              \
-  do {                                                                                                                   \
-    g.tag.set("k_linear_points_grad", {N, RECT, FMA, SI, SJ, PPL, AXR, CELL}, 0b00000110u);                              \
-    hipLaunchKernelGGL((k_linear_points_grad<T, N, RECT, FMA, SI, SJ, PPL, AXR, CELL>), dim3(blocks), dim3(kBlock), lds, stream, a); \
-    return hipGetLastError();                                                                                            \
-  } while (0)
-  if constexpr (N == 2) {
-    PG_GO(1, 1, 0);
-  } else {
-    if constexpr (sizeof(T) == 4) {
-      if (g.brick_cell == 2) PG_GO(1, 1, 2);
-    }
-    const int si = g.brick_step[0], sj = g.brick_step[1];
-    if (si == 1 && sj == 1) PG_GO(1, 1, 0);
-    if (si == 1 && sj == 2) PG_GO(1, 2, 0);
-    PG_GO(2, 2, 0);
-  }
-#undef PG_GO
-}
-
-template <typename T, int N, int PPL>
-static hipError_t pg_launch_kind(const GridDesc& g, PointsGradArgs<T, N>& a, size_t lds, size_t axis_lds, size_t npts, hipStream_t stream) {
-  const int axr = lane_axes_mode(g);  // axes in lanes (lane_axes.h) or 0 = LDS / L2 search
-  a.iters = brick_iters(g, npts, PPL, /*setup=*/g.kind != kRectilinear ? 0 : (axr == 0 ? 2 : 1));
-  const size_t nslots = (npts + PPL - 1) / PPL;
-  const size_t per_block = (size_t)kBlock * a.iters;
-  const unsigned blocks = (unsigned)((nslots + per_block - 1) / per_block);
-  if (g.kind == kRegular)
-    return g.fma ? pg_launch_steps<T, N, false, true, PPL, 0>(g, a, lds, blocks, stream)
-                 : pg_launch_steps<T, N, false, false, PPL, 0>(g, a, lds, blocks, stream);
-  if (axr == 2)
-    return g.fma ? pg_launch_steps<T, N, true, true, PPL, 2>(g, a, lds, blocks, stream)
-                 : pg_launch_steps<T, N, true, false, PPL, 2>(g, a, lds, blocks, stream);
-  if (axr == 3)
-    return g.fma ? pg_launch_steps<T, N, true, true, PPL, 3>(g, a, lds, blocks, stream)
-                 : pg_launch_steps<T, N, true, false, PPL, 3>(g, a, lds, blocks, stream);
-  if (axr == 1)
-    return g.fma ? pg_launch_steps<T, N, true, true, PPL, 1>(g, a, lds, blocks, stream)
-                 : pg_launch_steps<T, N, true, false, PPL, 1>(g, a, lds, blocks, stream);
-  return g.fma ? pg_launch_steps<T, N, true, true, PPL, 0>(g, a, lds + axis_lds, blocks, stream)
-               : pg_launch_steps<T, N, true, false, PPL, 0>(g, a, lds + axis_lds, blocks, stream);
-}
-
-template <typename T>
-static bool aligned2(const void* p) { return (reinterpret_cast<uintptr_t>(p) % (2 * sizeof(T))) == 0; }
+struct PointsGradKernel {
+  static constexpr const char* name = "k_linear_points_grad";
+  template <typename T, int N> using Args = PointsGradArgs<T, N>;
+  template <typename T, int N, bool RECT, bool FMA, int SI, int SJ, int PPL, int AXR, int CELL>
+  static auto kernel() { return &k_linear_points_grad<T, N, RECT, FMA, SI, SJ, PPL, AXR, CELL>; }
+};
 
 template <typename T, int N>
 static hipError_t pg_launch_linear(const GridDesc& g, const T* pts, size_t stride, T* out, T* grad, size_t gstride, size_t npts,
                                    unsigned long long* first_bad, hipStream_t stream) {
-  typedef typename LeafVec<T, 2>::type P;
   PointsGradArgs<T, N> a;
-  a.bricks = static_cast<const T*>(g.bricks);
   a.pts = pts;
   a.stride = stride;
   a.out = out;
   a.grad = grad;
   a.gstride = gstride;
-  a.first_bad = first_bad;
-  a.npts = npts;
-  for (int d = 0; d < N; ++d) {
-    a.start[d] = (T)g.start[d];
-    a.step[d] = (T)g.step[d];
-    a.n[d] = g.n[d];
-  }
-  a.nbj = g.brick_nb[1];
-  a.nbk = N == 3 ? g.brick_nb[2] : 1u;
-  const size_t lds = N == 3 ? (size_t)kBlock * kPieceRow * sizeof(P) + (size_t)kBlock * 16 : 0;
-  a.ax.use_lds = 0;
-  a.ax.image = nullptr;
-  a.ax.image_bytes = 0;
-  size_t axis_lds = 0;
-  // the 2-D kernel has no other LDS use: its axis image may take the wide budget, as in k_linear2_brick
-  if (g.kind == kRectilinear) axis_lds = fill_axis_args<T, N>(g, a.ax, /*big_lds=*/N == 2, /*records=*/true);
-  // two points per lane (one vector store of the values) when `out` is aligned to 2 * sizeof(T); the handle's `ppl`
-  // option = 1 forces the scalar form, as for the value kernels
-  const bool two = aligned2<T>(out) && g.cfg.ppl != 1;
-  // the coordinate load: k_linear_points' rule
-  a.load = kPointsLoadElem;
-  if (stride == (size_t)N && aligned2<T>(pts)) {
-    a.load = kPointsLoadWide;
-    if (N == 3 && sizeof(T) == 8 && two && g.cfg.points_load != kPointsLoadWide) a.load = kPointsLoadLds;
-  }
-  if (g.cfg.points_load == 3) a.load = kPointsLoadElem;
+  const bool two = cell_two_points<T>(g, {out});  // one vector store of the values
+  a.load = points_load_form<T, N>(g, pts, stride, two);
   // the gradient-row store: packed rows whose base is aligned to two elements take vector stores of the lane's own
   // elements (every lane's first element is then aligned too: PPL * N is even, or the form is not compiled), and in 3-D
   // f64 with two points per lane the wave's span through LDS unless option points_store = 1 keeps the per-lane stores:
@@ -113,8 +47,7 @@ static hipError_t pg_launch_linear(const GridDesc& g, const T* pts, size_t strid
     if (N == 3 && sizeof(T) == 8 && two && g.cfg.points_store != kPointsStoreWide) a.store = kPointsStoreLds;
   }
   if (g.cfg.points_store == 3) a.store = kPointsStoreElem;
-  if (two) return pg_launch_kind<T, N, 2>(g, a, lds, axis_lds, npts, stream);
-  return pg_launch_kind<T, N, 1>(g, a, lds, axis_lds, npts, stream);
+  return cell_launch<PointsGradKernel, T, N>(g, a, npts, first_bad, two, stream);
 }
 
 template <typename T, int N, bool RECT, bool FMA>

@@ -3,10 +3,11 @@
 // points first or interleaving the components afterwards.
 //
 //   k_linear_points_grad<T, N, RECT, FMA, SI, SJ, PPL, AXR, CELL>   N = 2, 3 multilinear on the re-laid table the handle
-//       already has.  The coordinate load is k_linear_points' (all three forms, PointsGradArgs::load); cell search, t,
-//       the gather, the value tree and the gradient arithmetic are k_linear_grad's statements, so `out` and `grad` have
-//       the bits of interpn_hip_eval_grad_device on the de-interleaved columns.  Only the gradient-row store is new
-//       (PointsGradArgs::store, launch-uniform):
+//       already has.  The coordinate load is the one k_linear_points expands (all three forms, PointsGradArgs::load);
+//       prologue, cell search, t, the gather, the value tree and the gradient arithmetic are the shared cell body of
+//       linear_cell.h, so `out` and `grad` have the bits of interpn_hip_eval_grad_device on the de-interleaved columns.
+//       The kernel's own are the 32-bit row addressing, the two pins and the gradient-row store (PointsGradArgs::store,
+//       launch-uniform):
 //         kPointsStoreElem   one element store per component: any stride, any alignment; also the ragged tail
 //         kPointsStoreWide   gstride == N, base aligned to two elements: the lane's own PPL * N contiguous elements as
 //                            two-element vector stores (the mirror of kPointsLoadWide)
@@ -33,8 +34,7 @@
 #pragma once
 
 #include "cubic_grad.h"
-#include "linear_grad.h"
-#include "points_forms.h"
+#include "linear_cell.h"
 
 // The pins of k_linear_points_grad (see above).  INTERPN_POINTS_GRAD_NO_PINS builds the kernel without them, for
 // `make variant` measurements only (DESIGN.md section 14 has the figures); the product is never built that way.
@@ -70,27 +70,12 @@ template <typename T, int N, bool RECT, bool FMA, int SI, int SJ, int PPL, int A
 __global__ void __launch_bounds__(kBlock) k_linear_points_grad(const PointsGradArgs<T, N> a) {
   static_assert(N == 2 || N == 3, "fused point-major gradient kernel: N = 2, 3");
   static_assert(CELL == 0 || (CELL == 2 && N == 3 && sizeof(T) == 4 && SI == 1 && SJ == 1), "2 x 4 x 4 bricks: 3-D f32");
-  typedef typename LeafVec<T, 2>::type P;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  // N == 3: [pieces][offsets][axes] as in k_linear_brick; N == 2: the axes alone (the gather is a lane-pair swap)
-  constexpr size_t kGatherLds = N == 3 ? (size_t)kBlock * kPieceRow * sizeof(P) + (size_t)kBlock * 16 : 0;
-  P* lds_piece = reinterpret_cast<P*>(smem_raw);
-  lds_u32* lds_off = reinterpret_cast<lds_u32*>(smem_raw + kBlock * kPieceRow * sizeof(P));
-  unsigned char* lds_axes = smem_raw + kGatherLds;
-  LaneAxes<T, N> la;
-  if constexpr (RECT && AXR != 0) {
-    la = load_lane_axes<T, N, AXR>(a.ax);
-  } else if (RECT && a.ax.use_lds) {
-    stage_axes<T, N>(a.ax, lds_axes);
-  }
-  const unsigned char* axis_base = (RECT && AXR == 0 && a.ax.use_lds) ? lds_axes : a.ax.image;
+  INTERPN_CELL_PROLOGUE();
   const unsigned lane = threadIdx.x;
   const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(lane >> 6));
   const size_t nslots = (a.npts + PPL - 1) / PPL;
   const size_t first = (size_t)blockIdx.x * a.iters * kBlock;
   typedef T TV __attribute__((ext_vector_type(2)));  // naturally aligned: vector accesses of the wide forms and of `out`
-  constexpr bool kCanWide = (PPL * N) % 2 == 0;
-  constexpr bool kCanLds = N == 3 && sizeof(T) == 8 && PPL == 2;
   for (unsigned it = 0; it < a.iters; ++it) {
     // every lane runs every iteration (dead lanes still fetch pieces for their quad / pair)
     // per lane everything is a 32-bit offset from the iteration's uniform first point p0 (the launcher keeps the strides
@@ -111,153 +96,23 @@ __global__ void __launch_bounds__(kBlock) k_linear_points_grad(const PointsGradA
     for (int h = 0; h < PPL; ++h)
 #pragma unroll
       for (int d = 0; d < N; ++d) xin[h][d] = RECT ? (T)0 : a.start[d];
-    // ---- the coordinate load of k_linear_points
-    bool loaded = false;
-    if constexpr (kCanLds) {
-      const unsigned wl = lane & 63u;
-      const unsigned wave_lp = wave * 64u * PPL;  // the wave's first point, from p0; it has 64 * PPL of them
-      if (a.load == kPointsLoadLds && wave_lp + 64 * PPL <= left) {  // wave-uniform
-        typedef T V16 __attribute__((ext_vector_type(2), aligned(16)));
-        // the wave's quads' rows of the piece area: 16 quads x 4 rows x kPieceRow slots, idle until the gather
-        P* mine = lds_piece + (size_t)wave * 16 * 4 * kPieceRow;
-        static_assert(16 * 4 * kPieceRow >= 64 * PPL * N / 2, "a wave's span fits its part of the piece area");
-        const V16* src = reinterpret_cast<const V16*>(a.pts + (p0 + wave_lp) * N);
-        V16 r[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) r[k] = stream_load(src + k * 64 + wl);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) *reinterpret_cast<V16*>(mine + k * 64 + wl) = r[k];
-        wave_sync();
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const P w = mine[wl * 3 + k];
-          xin[(2 * k) / N][(2 * k) % N] = w.x;
-          xin[(2 * k + 1) / N][(2 * k + 1) % N] = w.y;
-        }
-        wave_sync();
-        loaded = true;
-      }
-    }
-    if constexpr (kCanWide) {
-      if (!loaded && a.load != kPointsLoadElem && live[PPL - 1]) {
-        const TV* src = reinterpret_cast<const TV*>(a.pts + p0 * N);
-#pragma unroll
-        for (int k = 0; k < PPL * N / 2; ++k) {
-          const TV w = stream_load(src + (lp * N / 2 + k));
-          xin[(2 * k) / N][(2 * k) % N] = w.x;
-          xin[(2 * k + 1) / N][(2 * k + 1) % N] = w.y;
-        }
-        loaded = true;
-      }
-    }
-    if (!loaded) {  // any stride or alignment, and the batch's ragged tail
-#pragma unroll
-      for (int h = 0; h < PPL; ++h)
-        if (live[h]) {
-          const T* rows = a.pts + p0 * a.stride;
-#pragma unroll
-          for (int d = 0; d < N; ++d) xin[h][d] = stream_load(rows + ((lp + h) * (unsigned)a.stride + d));
-        }
-    }
-    // ---- cell search, gather, value tree and gradient arithmetic of k_linear_grad
+    const unsigned wl = lane & 63u;
+    const unsigned wave_lp = wave * 64u * PPL;  // the wave's first point, from p0; it has 64 * PPL of them
+    INTERPN_POINTS_LOAD(wave, wave_lp + 64 * PPL <= left, a.pts + (p0 + wave_lp) * N, a.pts + p0 * N, lp * N / 2, a.pts + p0 * a.stride,
+                        (lp + h) * (unsigned)a.stride);
     int cell_r[PPL][N];
     T x0_r[PPL][N], x1_r[PPL][N];
     if constexpr (RECT && AXR != 0) lane_axes_locate<T, N, PPL, AXR>(a.ax, la, xin, cell_r, x0_r, x1_r);
     T resv[PPL], gradv[N][PPL];
 #pragma unroll
     for (int h = 0; h < PPL; ++h) {
-      T t[N], width[N];
-      int loc[N];
-      bool ok = true;
-#pragma unroll
-      for (int d = 0; d < N; ++d) {
-        const T x = xin[h][d];
-        if (RECT) {
-          T x0, x1;
-          int l;
-          if constexpr (AXR != 0) {
-            l = cell_r[h][d];
-            x0 = x0_r[h][d];
-            x1 = x1_r[h][d];
-          } else {
-            const Axis<T> ax = make_axis<T, N>(a.ax, axis_base, d);
-            l = axis_cell<T>(ax, x, &x0, &x1);  // multilinear/rectilinear.rs:353-370, :310-311
-          }
-          const T step = x1 - x0;
-          t[d] = (x - x0) / step;  // rectilinear.rs:310-313
-          width[d] = step;
-          loc[d] = l;
-        } else {
-          T floc;
-          ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);  // multilinear/regular.rs:415-418
-          const int l = clamp_loc<T>(floc, a.n[d] - 2);             // regular.rs:420-422
-          const T izl = mul_add<FMA>(a.step[d], (T)l, a.start[d]);  // regular.rs:334-337
-          t[d] = (x - izl) / a.step[d];                             // regular.rs:339
-          width[d] = a.step[d];
-          loc[d] = l;
-        }
-      }
-      if (!RECT && !ok && live[h]) atomicMin(a.first_bad, (unsigned long long)(p0 + lp + h));
+      INTERPN_CELL_SEARCH(xin[h], cell_r[h], x0_r[h], x1_r[h], live[h], p0 + lp + h);
       if constexpr (N == 3) {
-        typedef BrickGeom<T, CELL> Geom;
-        const unsigned q = lane & 3;
-        const unsigned quad = lane >> 2;
-        const unsigned bk = (unsigned)loc[2] / (unsigned)Geom::SK;
-        const unsigned kpart = bk * (unsigned)Geom::ELEMS + ((unsigned)loc[2] - bk * (unsigned)Geom::SK);
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-          lds_off[(quad * 4 + p) * 4 + q] = brick_piece<T, SI, SJ, CELL>(a.nbj, a.nbk, loc[0], loc[1], kpart, p >> 1, p & 1);
-        wave_sync();
-        const uint4 toff = *reinterpret_cast<const uint4*>(&lds_off[(quad * 4 + q) * 4]);
-        const Cell<T> c = gather_cell<T>(a.bricks, toff, 0u, lds_piece, quad, q);
-        // value: the tree of k_linear_brick (i first, k last; multilinear/regular.rs:347-403)
-        T r[2];
-#pragma unroll
-        for (int dk = 0; dk < 2; ++dk) {
-          const T c0 = grad_lerp<FMA>(t[0], c.v[0][0][dk], c.v[1][0][dk]);
-          const T c1 = grad_lerp<FMA>(t[0], c.v[0][1][dk], c.v[1][1][dk]);
-          r[dk] = grad_lerp<FMA>(t[1], c0, c1);
-        }
-        resv[h] = grad_lerp<FMA>(t[2], r[0], r[1]);
-        // d/dx0: differences along i, reduced over j then k
-        T s[2];
-#pragma unroll
-        for (int dk = 0; dk < 2; ++dk)
-          s[dk] = grad_lerp<FMA>(t[1], c.v[1][0][dk] - c.v[0][0][dk], c.v[1][1][dk] - c.v[0][1][dk]);
-        gradv[0][h] = grad_lerp<FMA>(t[2], s[0], s[1]) / width[0];
-        // d/dx1: differences along j, reduced over i then k
-#pragma unroll
-        for (int dk = 0; dk < 2; ++dk)
-          s[dk] = grad_lerp<FMA>(t[0], c.v[0][1][dk] - c.v[0][0][dk], c.v[1][1][dk] - c.v[1][0][dk]);
-        gradv[1][h] = grad_lerp<FMA>(t[2], s[0], s[1]) / width[1];
-        // d/dx2: differences along k, reduced over i then j
-#pragma unroll
-        for (int dj = 0; dj < 2; ++dj)
-          s[dj] = grad_lerp<FMA>(t[0], c.v[0][dj][1] - c.v[0][dj][0], c.v[1][dj][1] - c.v[1][dj][0]);
-        gradv[2][h] = grad_lerp<FMA>(t[1], s[0], s[1]) / width[2];
+        INTERPN_CELL_VALUE3(resv[h]);
+        INTERPN_CELL_GRAD3(gradv[0][h], gradv[1][h], gradv[2][h]);
       } else {
-        // the lane-pair gather of k_linear2_brick: brick (bi = i, bj = j / SJ2), two row pieces per point
-        constexpr unsigned KW2 = 64 / sizeof(T), SJ2 = KW2 - 1, EL2 = 2 * KW2;
-        const unsigned q = lane & 1;
-        const unsigned bj = (unsigned)loc[1] / SJ2;
-        const unsigned mine = ((unsigned)loc[0] * a.nbj + bj) * EL2 + ((unsigned)loc[1] - bj * SJ2);
-        const unsigned theirs = grad_swap1(mine);
-        const unsigned off0 = (q == 0 ? mine : theirs) + q * KW2;
-        const unsigned off1 = (q == 0 ? theirs : mine) + q * KW2;
-        const P p0 = *reinterpret_cast<const P*>(a.bricks + off0);
-        const P p1 = *reinterpret_cast<const P*>(a.bricks + off1);
-        const P keep = q == 0 ? p0 : p1;
-        const P send = q == 0 ? p1 : p0;
-        P recv;
-        recv.x = grad_swap1(send.x);
-        recv.y = grad_swap1(send.y);
-        const P row0 = q == 0 ? keep : recv;  // v(i, j), v(i, j+1)
-        const P row1 = q == 0 ? recv : keep;  // row i+1
-        const T c0 = grad_lerp<FMA>(t[0], row0.x, row1.x);
-        const T c1 = grad_lerp<FMA>(t[0], row0.y, row1.y);
-        resv[h] = grad_lerp<FMA>(t[1], c0, c1);
-        gradv[0][h] = grad_lerp<FMA>(t[1], row1.x - row0.x, row1.y - row0.y) / width[0];
-        gradv[1][h] = grad_lerp<FMA>(t[0], row0.y - row0.x, row1.y - row1.x) / width[1];
+        INTERPN_CELL_VALUE2(resv[h]);
+        INTERPN_CELL_GRAD2(gradv[0][h], gradv[1][h]);
       }
       if (h + 1 < PPL) {  // this point's results are complete here: they are not left to be computed behind the next gather
         INTERPN_POINTS_GRAD_PIN(resv[h]);
@@ -286,8 +141,6 @@ __global__ void __launch_bounds__(kBlock) k_linear_points_grad(const PointsGradA
     // ---- the gradient-row store: element e of the lane's PPL * N is component e % N of its point e / N
     bool stored = false;
     if constexpr (kCanLds) {
-      const unsigned wl = lane & 63u;
-      const unsigned wave_lp = wave * 64u * PPL;
       if (a.store == kPointsStoreLds && wave_lp + 64 * PPL <= left) {  // wave-uniform
         typedef T V16 __attribute__((ext_vector_type(2), aligned(16)));
         P* mine = lds_piece + (size_t)wave * 16 * 4 * kPieceRow;  // idle: the last gather has read its pieces back
