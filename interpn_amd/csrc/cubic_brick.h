@@ -20,8 +20,8 @@
 // to the C-order kernels.  Table reads are raw buffer loads (32-bit byte offset per lane, plane
 // offset in the scalar operand): no vector address arithmetic, range-checked.
 #pragma once
+#include "cubic_cell.h"
 #include "rect_args.h"
-
 
 namespace interpn {
 
@@ -319,26 +319,7 @@ template <typename T, int N, bool RECT, bool FMA, int SI, int SJ>
 __global__ void __launch_bounds__(kBlock) k_cubic_brick(const CubicBrickArgs<T, N> a) {
   typedef typename CubicDimSel<T, RECT>::type DimT;
   if (a.gate && __hip_atomic_load(a.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;  // (launch-uniform)
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  // One region, used first for the offset transpose (u32) and then for the data transposes (T).
-  typedef T __attribute__((may_alias)) lds_T;
-  lds_T* lds_data = reinterpret_cast<lds_T*>(smem_raw);
-  lds_u32* lds_off = reinterpret_cast<lds_u32*>(smem_raw);
-  constexpr bool DMA = cubic_dma<T, SI, SJ>();
-  constexpr size_t kRegion = cubic_lds_region<T, SI, SJ>();
-  unsigned char* lds_axes = smem_raw + kRegion;
-  if (RECT && a.ax.use_lds) stage_axes<T, N>(a.ax, lds_axes);
-  const unsigned char* axis_base = (RECT && a.ax.use_lds) ? lds_axes : a.ax.image;
-  const unsigned lane = threadIdx.x;
-  const unsigned me = lane & 15;
-  const unsigned group = lane >> 4;
-  // The offset matrix of a group lives inside the SAME bytes as its data matrix (both regions are
-  // private to the group's wave): index it with the data matrix' group stride.
-  const unsigned goff = group * (unsigned)(16 * kCubRow * sizeof(T) / 4);
-  const __amdgpu_buffer_rsrc_t rsrc = table_rsrc(a.bricks, a.table_bytes);
-  // LDS byte address of this wave's tile image (LDS-DMA gather), in a scalar register
-  const unsigned lds_wave = (unsigned)__builtin_amdgcn_readfirstlane(
-      (int)((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_raw + (lane >> 6) * cubic_dma_image<T>()));
+  INTERPN_CUBIC_BRICK_PROLOGUE()
   const size_t nthreads = (size_t)gridDim.x * kBlock;
   const size_t per_xcd = (size_t)(gridDim.x >> 3) * kBlock;  // points one XCD's workgroups cover per iteration
   const size_t niter = a.eighth ? (a.eighth + per_xcd - 1) / per_xcd : (a.npts + nthreads - 1) / nthreads;
@@ -365,57 +346,16 @@ __global__ void __launch_bounds__(kBlock) k_cubic_brick(const CubicBrickArgs<T, 
         else loc[d] = cubic_rect_locate<T, true>(ax, x, a.linearize, /*fma_linear=*/false, dim[d]);  // multicubic/rectilinear.rs:366-408
       } else {
         const T x = live ? stream_load(a.obs[d] + i0) : a.start[d];
-        T floc;
-        ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);   // multicubic/regular.rs:435-438
-        ok &= floc != (T)-9223372036854775808.0;                  // `- 1` would overflow isize
-        const T nn = (T)a.n[d];
-        const int l = clamp_loc<T>(floc - (T)1, a.n[d] - 4);      // regular.rs:440-442
-        int sat;
-        bool outside;
-        if (floc < (T)0) { sat = kSatLow; outside = true; }       // regular.rs:445-466 on floc = iloc + 1
-        else if (floc == (T)0) { sat = kSatLow; outside = false; }
-        else if (floc > nn - (T)2) { sat = kSatHigh; outside = true; }
-        else if (floc == nn - (T)2) { sat = kSatHigh; outside = false; }
-        else { sat = kSatNone; outside = false; }
-        const T index_one_loc = mul_add<false>(a.step[d], (T)(l + 1), a.start[d]);  // regular.rs:356-360, never fused
-        const T t = (x - index_one_loc) / a.step[d];
-        dim[d].sat = sat;
-        dim[d].linear = (outside && a.linearize) ? 1 : 0;
-        dim[d].tt = sat == kSatLow ? -t : (sat == kSatHigh ? t - (T)1 : t);
+        INTERPN_CUBIC_LOCATE(x, a.start[d], a.step[d], a.n[d], a.linearize, dim[d], ok)
         loc[d] = l;
       }
     }
     if (!RECT && !ok && live) atomicMin(a.first_bad, (unsigned long long)(a.index_base + dst));
-    // Offsets of my point's 16 footprint elements (plane base included) -> LDS, transposed.
+    // the table offsets of my point's footprint, plane base included
     unsigned pbase = 0;  // element offsets here, bytes in LDS
 #pragma unroll
     for (int d = 2; d < N; ++d) pbase += (unsigned)loc[d] * a.plane_stride[d];
-    unsigned toff[16];
-    if constexpr (DMA) {
-      // my point's tile (steps 1,1: tile index = cell) as a byte offset; instruction q of a plane's
-      // DMA has me fetch piece c of point p (gather_plane_dma)
-      constexpr unsigned PP = (unsigned)sizeof(T);  // 16-byte pieces per tile; 64 / PP points per DMA instruction
-      const unsigned wl = lane & 63u;
-      const unsigned tb = (pbase + (unsigned)(loc[0] * (int)a.nbj + loc[1]) * 16u) * (unsigned)sizeof(T);
-#pragma unroll
-      for (int q = 0; q < (int)PP; ++q) {
-        const unsigned p = ((unsigned)q * 64u + wl) / PP;
-        const unsigned c = ((wl & (PP - 1u)) - cubic_dma_rot<T>(p)) & (PP - 1u);
-        toff[q] = (unsigned)__shfl((int)tb, (int)p) + c * 16u;
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        int bi, oi, bj, oj;
-        tile_coord<SI>(loc[0], e >> 2, &bi, &oi);
-        tile_coord<SJ>(loc[1], e & 3, &bj, &oj);
-        lds_off[goff + e * kCubRow + me] = (pbase + ((unsigned)(bi * (int)a.nbj + bj) * 16u) + (unsigned)(oi * 4 + oj)) * (unsigned)sizeof(T);
-      }
-      wave_sync();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) toff[r] = lds_off[goff + me * kCubRow + r];
-      wave_sync();
-    }
+    INTERPN_CUBIC_TILE_OFFSETS()
     // bit d set: every lane of this wave is interior along dim d (d = 0, 1; regular grids)
     unsigned interior = 0;
     if constexpr (!RECT) {

@@ -16,9 +16,11 @@
 //       one partial per component d <= level.  No binned / gated forms, no per-cell records, no interior-wave or packed-f32
 //       shortcuts; rectilinear nodes divide as the reference writes them (cubic_rect_node's divisions: the fast form with
 //       its whole-wave second evaluation would double the 12 live partials of a 3-D f64 point for a path that pays for
-//       sorted points, which a gradient call does not have).
-//   k_cubic_grad_n<T, KIND, FMA>   runtime N = 1..8 on the C-ordered grid: the value walk of k_generic, then one walk per
-//       component with D at level d.  Written for correctness, not tuned.
+//       sorted points, which a gradient call does not have).  The kernel is its coordinate load, the gradient cell of
+//       cubic_cell.h (INTERPN_CUBIC_BRICK_PROLOGUE, INTERPN_CUBIC_GRAD_CELL: shared with k_cubic_points_grad, points_grad.h)
+//       on the nodes and gathers below, and its stores.
+//   k_cubic_grad_n<T, KIND, FMA>   runtime N = 1..8 on the C-ordered grid: the locate step (INTERPN_CUBIC_CLASS) and value
+//       walk of k_generic, then one walk per component with D at level d.  Written for correctness, not tuned.
 #pragma once
 
 #include "cubic_brick.h"
@@ -162,124 +164,19 @@ __device__ __forceinline__ void grad_gather_tile(__amdgpu_buffer_rsrc_t bricks, 
 template <typename T, int N, bool RECT, bool FMA, int SI, int SJ>
 __global__ void __launch_bounds__(kBlock) k_cubic_grad(const CubicGradArgs<T, N> a) {
   static_assert(N == 2 || N == 3, "fused multicubic gradient kernel: N = 2, 3");
-  typedef typename CubicDimSel<T, RECT>::type DimT;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  typedef T __attribute__((may_alias)) lds_T;
-  lds_T* lds_data = reinterpret_cast<lds_T*>(smem_raw);
-  lds_u32* lds_off = reinterpret_cast<lds_u32*>(smem_raw);
-  constexpr bool DMA = cubic_dma<T, SI, SJ>();
-  constexpr size_t kRegion = cubic_lds_region<T, SI, SJ>();
-  constexpr int NP = N == 2 ? 1 : 4;  // planes of a point
-  unsigned char* lds_axes = smem_raw + kRegion;
-  if (RECT && a.ax.use_lds) stage_axes<T, N>(a.ax, lds_axes);
-  const unsigned char* axis_base = (RECT && a.ax.use_lds) ? lds_axes : a.ax.image;
-  const unsigned lane = threadIdx.x;
-  const unsigned me = lane & 15;
-  const unsigned group = lane >> 4;
-  const unsigned goff = group * (unsigned)(16 * kCubRow * sizeof(T) / 4);
-  const __amdgpu_buffer_rsrc_t rsrc = table_rsrc(a.bricks, a.table_bytes);
-  const unsigned lds_wave = (unsigned)__builtin_amdgcn_readfirstlane(
-      (int)((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_raw + (lane >> 6) * cubic_dma_image<T>()));
+  INTERPN_CUBIC_BRICK_PROLOGUE()
   const size_t nthreads = (size_t)gridDim.x * kBlock;
   const size_t niter = (a.npts + nthreads - 1) / nthreads;
   for (size_t it = 0; it < niter; ++it) {
     // every lane runs every iteration: dead lanes take part in the gathers' exchanges with the offsets of a valid point
     const size_t i0 = it * nthreads + (size_t)blockIdx.x * kBlock + lane;
     const bool live = i0 < a.npts;
-    DimT dim[N];
-    int loc[N];
-    T width[N];
-    bool ok = true;
-#pragma unroll
-    for (int d = 0; d < N; ++d) {
-      if constexpr (RECT) {
-        const T x = live ? stream_load(a.obs[d] + i0) : (T)0;
-        const Axis<T> ax = make_axis<T, N>(a.ax, axis_base, d);
-        loc[d] = cubic_rect_locate<T>(ax, x, a.linearize, /*fma_linear=*/false, dim[d]);  // multicubic/rectilinear.rs:366-408
-        width[d] = cubic_rect_width<T>(ax.g, loc[d], dim[d].sat);
-      } else {
-        const T x = live ? stream_load(a.obs[d] + i0) : a.start[d];
-        T floc;
-        ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);   // multicubic/regular.rs:435-438
-        ok &= floc != (T)-9223372036854775808.0;                  // `- 1` would overflow isize
-        const T nn = (T)a.n[d];
-        const int l = clamp_loc<T>(floc - (T)1, a.n[d] - 4);      // regular.rs:440-442
-        int sat;
-        bool outside;
-        if (floc < (T)0) { sat = kSatLow; outside = true; }       // regular.rs:445-466 on floc = iloc + 1
-        else if (floc == (T)0) { sat = kSatLow; outside = false; }
-        else if (floc > nn - (T)2) { sat = kSatHigh; outside = true; }
-        else if (floc == nn - (T)2) { sat = kSatHigh; outside = false; }
-        else { sat = kSatNone; outside = false; }
-        const T index_one_loc = mul_add<false>(a.step[d], (T)(l + 1), a.start[d]);  // regular.rs:356-360, never fused
-        const T t = (x - index_one_loc) / a.step[d];
-        dim[d].sat = sat;
-        dim[d].linear = (outside && a.linearize) ? 1 : 0;
-        dim[d].tt = sat == kSatLow ? -t : (sat == kSatHigh ? t - (T)1 : t);
-        loc[d] = l;
-        width[d] = a.step[d];
-      }
-    }
-    if (!RECT && !ok && live) atomicMin(a.first_bad, (unsigned long long)i0);
-    unsigned pbase = 0;  // element offsets here, bytes in LDS
-    if constexpr (N == 3) pbase = (unsigned)loc[2] * a.plane_stride[2];
-    unsigned toff[16];
-    if constexpr (DMA) {
-      constexpr unsigned PP = (unsigned)sizeof(T);
-      const unsigned wl = lane & 63u;
-      const unsigned tb = (pbase + (unsigned)(loc[0] * (int)a.nbj + loc[1]) * 16u) * (unsigned)sizeof(T);
-#pragma unroll
-      for (int q = 0; q < (int)PP; ++q) {
-        const unsigned p = ((unsigned)q * 64u + wl) / PP;
-        const unsigned c = ((wl & (PP - 1u)) - cubic_dma_rot<T>(p)) & (PP - 1u);
-        toff[q] = (unsigned)__shfl((int)tb, (int)p) + c * 16u;
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        int bi, oi, bj, oj;
-        tile_coord<SI>(loc[0], e >> 2, &bi, &oi);
-        tile_coord<SJ>(loc[1], e & 3, &bj, &oj);
-        lds_off[goff + e * kCubRow + me] = (pbase + ((unsigned)(bi * (int)a.nbj + bj) * 16u) + (unsigned)(oi * 4 + oj)) * (unsigned)sizeof(T);
-      }
-      wave_sync();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) toff[r] = lds_off[goff + me * kCubRow + r];
-      wave_sync();
-    }
-    auto delta_of = [&](int k) -> unsigned {  // byte offset of plane k along dim 2
-      if constexpr (N == 3) return (unsigned)k * a.plane_stride[2] * (unsigned)sizeof(T);
-      else return 0u;
-    };
-    // per plane: the value, d/dx0 and d/dx1 after dims 0 and 1; planes in the reference's order (dim 2 ascending)
-    T sv[NP], s0[NP], s1[NP];
-    if constexpr (DMA) dma_issue_plane<T>(rsrc, toff, delta_of(0), lds_wave);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      T v[16];
-      if constexpr (DMA) {
-        dma_take_tile<T>(lds_wave, lane & 63u, v);
-        if (k + 1 < NP) dma_issue_plane<T>(rsrc, toff, delta_of(k + 1), lds_wave);
-      } else {
-        grad_gather_tile<T>(rsrc, toff, delta_of(k), lds_data, group, me, v);
-      }
-      grad_reduce_tile<T, RECT, FMA>(v, dim, sv[k], s0[k], s1[k]);
-    }
-    T res, g[N];
-    if constexpr (N == 2) {
-      res = sv[0];
-      g[0] = s0[0];
-      g[1] = s1[0];
-    } else {
-      cubic_node_vd<RECT, FMA, T>(sv[0], sv[1], sv[2], sv[3], dim[2], res, g[2]);
-      g[0] = cubic_node_sel<RECT, FMA, T>(s0[0], s0[1], s0[2], s0[3], dim[2]);
-      g[1] = cubic_node_sel<RECT, FMA, T>(s1[0], s1[1], s1[2], s1[3], dim[2]);
-    }
+    INTERPN_CUBIC_GRAD_CELL(live ? stream_load(a.obs[d] + i0) : (RECT ? (T)0 : a.start[d]), live, i0)
     if (live) {
       stream_store(a.out + i0, res);
 #pragma unroll
       for (int d = 0; d < N; ++d) {
-        const T s = dim[d].sat == kSatLow ? -g[d] : g[d];
+        const T s = INTERPN_CUBIC_GRAD_SIGNED(d);
         stream_store(a.grad[d] + i0, s / width[d]);
       }
     }
@@ -340,25 +237,16 @@ __global__ void __launch_bounds__(kBlock) k_cubic_grad_n(const CubicGradGenericA
       const T x = a.obs[d][i];
       int loc;
       if constexpr (KIND == kRegular) {
-        // k_generic's cubic locate step (multicubic/regular.rs:435-466)
         T floc;
         ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);
         ok &= floc != (T)-9223372036854775808.0;
-        const T n = (T)a.n[d];
-        loc = clamp_loc<T>(floc - (T)1, a.n[d] - 4);
-        int sat;
-        bool outside;
-        if (floc < (T)0) { sat = kSatLow; outside = true; }
-        else if (floc == (T)0) { sat = kSatLow; outside = false; }
-        else if (floc > n - (T)2) { sat = kSatHigh; outside = true; }
-        else if (floc == n - (T)2) { sat = kSatHigh; outside = false; }
-        else { sat = kSatNone; outside = false; }
-        const T iol = mul_add<false>(a.step[d], (T)(loc + 1), a.start[d]);
-        const T t = (x - iol) / a.step[d];
+        INTERPN_CUBIC_CLASS(floc, a.start[d], a.step[d], a.n[d])
+        loc = l;
+        const T t = (x - index_one_loc) / a.step[d];
         c_sat[d] = sat;
         c_lin[d] = (outside && a.linearize) ? 1 : 0;
         c_plain[d] = (a.fma_linear != 0 && sat == kSatLow && outside) ? 1 : 0;  // recursive arm's OutsideLow (regular_recursive.rs:536)
-        c_t[d] = sat == kSatLow ? -t : (sat == kSatHigh ? t - (T)1 : t);
+        c_t[d] = INTERPN_CUBIC_TT(t);
         c_w[d] = a.step[d];
       } else {
         Axis<T> ax;

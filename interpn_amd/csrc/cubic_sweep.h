@@ -88,22 +88,11 @@ __global__ void __launch_bounds__(THREADS) k_cubic_sweep(const CubicSweepArgs<T,
             ok &= regular_floc<T>(xx, a.start[d], a.step[d], &floc);   // multicubic/regular.rs:435-438
             ok &= floc != (T)-9223372036854775808.0;                   // `- 1` would overflow isize
           }
-          const T nn = (T)a.n[d];
-          const int l = clamp_loc<T>(floc - (T)1, a.n[d] - 4);       // regular.rs:440-442
-          int sat;
-          bool outside;
-          if (floc < (T)0) { sat = kSatLow; outside = true; }        // regular.rs:445-466 on floc = iloc + 1
-          else if (floc == (T)0) { sat = kSatLow; outside = false; }
-          else if (floc > nn - (T)2) { sat = kSatHigh; outside = true; }
-          else if (floc == nn - (T)2) { sat = kSatHigh; outside = false; }
-          else { sat = kSatNone; outside = false; }
-          const T index_one_loc = mul_add<false>(a.step[d], (T)(l + 1), a.start[d]);  // regular.rs:356-360, never fused
+          INTERPN_CUBIC_CLASS(floc, a.start[d], a.step[d], a.n[d])
           T t;
           if constexpr (FAST) exact = divide_fast(xx - index_one_loc, a.step[d], s.rstep[d], &t) && exact;
           else t = (xx - index_one_loc) / a.step[d];
-          dim[d].sat = sat;
-          dim[d].linear = (outside && a.linearize) ? 1 : 0;
-          dim[d].tt = sat == kSatLow ? -t : (sat == kSatHigh ? t - (T)1 : t);
+          INTERPN_CUBIC_DIM_FILL(dim[d], t, a.linearize)
           loc[d] = l;
         }
         return exact;

@@ -20,6 +20,7 @@
 // batch in one pass of small workgroups (interpn_host.h::brick_iters).
 #pragma once
 
+#include "cubic_cell.h"
 #include "interpn_device.h"
 #include "interpn_host.h"
 
@@ -214,30 +215,8 @@ __global__ void __launch_bounds__(kBlock) k_cubic_regular(const RegularArgs<T, N
 #pragma unroll
     for (int d = 0; d < N; ++d) {
       const T x = stream_load(a.obs[d] + i);
-      T floc;
-      ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);  // regular.rs:435-438
-      ok &= floc != (T)-9223372036854775808.0;  // `- 1` would overflow isize: the reference panics
-      // iloc = isize(floc) - 1.  All comparisons below are on floc (an integer-valued float),
-      // which is exact for |floc| < 2^63; beyond 2^53 neighbouring integers coincide in f64 but
-      // every threshold involved (−1, 0, n−3) is far below that.
-      const T n = (T)a.n[d];
-      const int loc = clamp_loc<T>(floc - (T)1, a.n[d] - 4);  // regular.rs:440-442
-      int sat;
-      bool outside;
-      // regular.rs:445-466 with iloc = floc-1: iloc < -1 <=> floc < 0; iloc == -1 <=> floc == 0;
-      // iloc > n-3 <=> floc > n-2; iloc == n-3 <=> floc == n-2.
-      if (floc < (T)0) { sat = kSatLow; outside = true; }
-      else if (floc == (T)0) { sat = kSatLow; outside = false; }
-      else if (floc > n - (T)2) { sat = kSatHigh; outside = true; }
-      else if (floc == n - (T)2) { sat = kSatHigh; outside = false; }
-      else { sat = kSatNone; outside = false; }
-      // regular.rs:356-360 — never fused
-      const T index_one_loc = mul_add<false>(a.step[d], (T)(loc + 1), a.start[d]);
-      const T t = (x - index_one_loc) / a.step[d];
-      dim[d].sat = sat;
-      dim[d].linear = (outside && a.linearize) ? 1 : 0;
-      dim[d].tt = sat == kSatLow ? -t : (sat == kSatHigh ? t - (T)1 : t);
-      base += (unsigned)loc * a.stride[d];
+      INTERPN_CUBIC_LOCATE(x, a.start[d], a.step[d], a.n[d], a.linearize, dim[d], ok)
+      base += (unsigned)l * a.stride[d];
     }
     if (!ok) atomicMin(a.first_bad, (unsigned long long)i);
     typedef CubicRegularNode<T, FMA> Node;
@@ -399,21 +378,13 @@ __global__ void __launch_bounds__(kBlock) k_generic(const GenericArgs<T> a) {
                                              : mul_add<false>(a.step[d], (T)loc, a.start[d]);
           tlin[d] = (x - izl) / a.step[d];
         } else {
-          const T n = (T)a.n[d];
-          loc = clamp_loc<T>(floc - (T)1, a.n[d] - 4);
-          int sat;
-          bool outside;
-          if (floc < (T)0) { sat = kSatLow; outside = true; }
-          else if (floc == (T)0) { sat = kSatLow; outside = false; }
-          else if (floc > n - (T)2) { sat = kSatHigh; outside = true; }
-          else if (floc == n - (T)2) { sat = kSatHigh; outside = false; }
-          else { sat = kSatNone; outside = false; }
-          const T iol = mul_add<false>(a.step[d], (T)(loc + 1), a.start[d]);
-          const T t = (x - iol) / a.step[d];
+          INTERPN_CUBIC_CLASS(floc, a.start[d], a.step[d], a.n[d])
+          loc = l;
+          const T t = (x - index_one_loc) / a.step[d];
           dreg[d].sat = sat;
           dreg[d].linear = (outside && a.linearize) ? 1 : 0;
           dreg[d].k1_plain = (a.fma_linear != 0 && sat == kSatLow && outside) ? 1 : 0;  // recursive arm's OutsideLow (regular_recursive.rs:536)
-          dreg[d].tt = sat == kSatLow ? -t : (sat == kSatHigh ? t - (T)1 : t);
+          dreg[d].tt = INTERPN_CUBIC_TT(t);
         }
       } else {
         const T* g = a.grid[d];
@@ -504,21 +475,13 @@ __global__ void __launch_bounds__(kBlock) k_generic_n(const GenericArgs<T> a) {
                                              : mul_add<false>(a.step[d], (T)loc, a.start[d]);
           tlin[d] = (x - izl) / a.step[d];
         } else {
-          const T n = (T)a.n[d];
-          loc = clamp_loc<T>(floc - (T)1, a.n[d] - 4);
-          int sat;
-          bool outside;
-          if (floc < (T)0) { sat = kSatLow; outside = true; }
-          else if (floc == (T)0) { sat = kSatLow; outside = false; }
-          else if (floc > n - (T)2) { sat = kSatHigh; outside = true; }
-          else if (floc == n - (T)2) { sat = kSatHigh; outside = false; }
-          else { sat = kSatNone; outside = false; }
-          const T iol = mul_add<false>(a.step[d], (T)(loc + 1), a.start[d]);
-          const T t = (x - iol) / a.step[d];
+          INTERPN_CUBIC_CLASS(floc, a.start[d], a.step[d], a.n[d])
+          loc = l;
+          const T t = (x - index_one_loc) / a.step[d];
           dreg[d].sat = sat;
           dreg[d].linear = (outside && a.linearize) ? 1 : 0;
           dreg[d].k1_plain = (a.fma_linear != 0 && sat == kSatLow && outside) ? 1 : 0;  // recursive arm's OutsideLow (regular_recursive.rs:536)
-          dreg[d].tt = sat == kSatLow ? -t : (sat == kSatHigh ? t - (T)1 : t);
+          dreg[d].tt = INTERPN_CUBIC_TT(t);
         }
       } else {
         const T* g = a.grid[d];

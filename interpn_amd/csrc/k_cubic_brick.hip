@@ -1,5 +1,6 @@
-// Launchers of the tiled multicubic kernels (cubic_brick.h).
-#include "cubic_brick.h"
+// Host side of the tiled multicubic table (cubic_brick.h): its geometry, its builder, and the launcher of k_cubic_brick,
+// which sets the kernel's own arguments (binned and gated forms, per-cell records) and goes through cubic_cell_launch.h.
+#include "cubic_cell_launch.h"
 
 namespace interpn {
 
@@ -28,60 +29,25 @@ hipError_t build_cubic_tiles(const GridDesc& g, void* tiles, hipStream_t stream)
   return hipGetLastError();
 }
 
-template <typename T, int N, bool RECT, bool FMA>
-static hipError_t launch_steps(const GridDesc& g, const CubicBrickArgs<T, N>& a, size_t lds, unsigned blocks, hipStream_t stream) {
-  const int si = g.brick_step[0], sj = g.brick_step[1];
-#define GO(SI, SJ) do { g.tag.set("k_cubic_brick", {N, RECT, FMA, SI, SJ}, 0b00110u); hipLaunchKernelGGL((k_cubic_brick<T, N, RECT, FMA, SI, SJ>), dim3(blocks), dim3(kBlock), lds, stream, a); } while (0)
-  if (si == 4 && sj == 4) GO(4, 4);
-  else if (si == 2 && sj == 4) GO(2, 4);
-  else if (si == 2 && sj == 2) GO(2, 2);
-  else if (si == 1 && sj == 4) GO(1, 4);
-  else if (si == 1 && sj == 1) GO(1, 1);
-  else return hipErrorInvalidValue;
-#undef GO
-  return hipGetLastError();
-}
+struct CubicBrickKernel {
+  static constexpr const char* name = "k_cubic_brick";
+  template <typename T, int N> using Args = CubicBrickArgs<T, N>;
+  template <typename T, int N, bool RECT, bool FMA, int SI, int SJ>
+  static auto kernel() { return &k_cubic_brick<T, N, RECT, FMA, SI, SJ>; }
+};
 
 template <typename T, int N>
 static hipError_t launch_n(const GridDesc& g, const T* const* obs, T* out, size_t npts, unsigned long long* first_bad,
                            hipStream_t stream, const unsigned* scatter, size_t index_base) {
   CubicBrickArgs<T, N> a;
-  a.bricks = static_cast<const T*>(g.bricks);
-  {
-    unsigned nb[2];
-    size_t bytes = 0;
-    cubic_tile_geometry(g, g.brick_step[0], g.brick_step[1], nb, &bytes);
-    a.table_bytes = (unsigned)bytes;  // < 4 GiB by construction (maybe_build_cubic_tiles)
-  }
   a.out = out;
-  a.first_bad = first_bad;
-  a.npts = npts;
   a.scatter = scatter;
   a.index_base = index_base;
-  a.linearize = g.linearize;
   for (int d = 0; d < N; ++d) {
     a.obs[d] = obs[d];
-    a.start[d] = (T)g.start[d];
-    a.step[d] = (T)g.step[d];
-    a.n[d] = g.n[d];
-    a.plane_stride[d] = 0;
-  }
-  a.nbj = g.brick_nb[1];
-  // table[plane index (dims 2..N-1, C order)][bi][bj][16]
-  unsigned acc = g.brick_nb[0] * g.brick_nb[1] * 16u;
-  for (int d = N - 1; d >= 2; --d) {
-    a.plane_stride[d] = acc;
-    acc *= (unsigned)g.n[d];
-  }
-  const bool dma = g.brick_step[0] == 1 && g.brick_step[1] == 1;  // cubic_brick.h::cubic_dma
-  size_t lds = dma ? (size_t)(kBlock / 64) * cubic_dma_image<T>() : (size_t)kBlock * kCubRow * (sizeof(T) > 4 ? sizeof(T) : 4);
-  a.ax.use_lds = 0;
-  a.ax.image = nullptr;
-  a.ax.image_bytes = 0;
-  if (g.kind == kRectilinear) lds += fill_axis_args<T, N>(g, a.ax);
-  for (int d = 0; d < N; ++d)
     a.crec[d] = (g.kind == kRectilinear && g.axis_crec_bytes)
                     ? reinterpret_cast<const CubicCellRecord<T>*>(static_cast<const unsigned char*>(g.axis_image) + g.axis_crec_off[d]) : nullptr;
+  }
   unsigned blocks = grid_blocks(npts, 1, g.cfg);
   a.gate = scatter ? nullptr : g.launch_gate;
   a.eighth = 0;
@@ -89,11 +55,7 @@ static hipError_t launch_n(const GridDesc& g, const T* const* obs, T* out, size_
     blocks &= ~7u;  // eight equal XCD shares; the grid-stride loop covers what the rounding drops
     a.eighth = ((npts + 7) / 8 + kBlock - 1) / kBlock * kBlock;
   }
-  if (g.kind == kRegular)
-    return g.fma ? launch_steps<T, N, false, true>(g, a, lds, blocks, stream)
-                 : launch_steps<T, N, false, false>(g, a, lds, blocks, stream);
-  return g.fma ? launch_steps<T, N, true, true>(g, a, lds, blocks, stream)
-               : launch_steps<T, N, true, false>(g, a, lds, blocks, stream);
+  return cubic_cell_launch<CubicBrickKernel, T, N>(g, a, npts, first_bad, blocks, stream);
 }
 
 template <typename T>

@@ -1,66 +1,29 @@
-// Host side of the multicubic value-and-gradient evaluation (cubic_grad.h): which of the two kernels a handle gets, and
-// their launchers.  One launch per call whatever the batch size: the binned and column paths have no gradient form.
+// Host side of the multicubic value-and-gradient evaluation (cubic_grad.h): which of the two kernels a handle gets
+// (cubic_grad_fused_applies, cubic_cell_launch.h), the fused kernel's own arguments in front of the shared launcher of
+// cubic_cell_launch.h, and the launcher of the runtime-N kernel.  One launch per call whatever the batch size: the binned
+// and column paths have no gradient form.
+#include "cubic_cell_launch.h"
 #include "cubic_grad.h"
 
 namespace interpn {
 
-// The fused kernel runs where the handle keeps the tiled table it gathers from (N = 2, 3; a 4-D handle's tiles are
-// left to the runtime-N kernel).
-static bool cubic_grad_fused_applies(const GridDesc& g) {
-  return g.method == kCubic && g.bricks && !g.cfg.force_generic && (g.ndims == 2 || g.ndims == 3);
-}
-
-template <typename T, int N, bool RECT, bool FMA>
-static hipError_t cubic_grad_launch_steps(const GridDesc& g, const CubicGradArgs<T, N>& a, size_t lds, unsigned blocks, hipStream_t stream) {
-  const int si = g.brick_step[0], sj = g.brick_step[1];
-#define GO(SI, SJ) do { g.tag.set("k_cubic_grad", {N, RECT, FMA, SI, SJ}, 0b00110u); hipLaunchKernelGGL((k_cubic_grad<T, N, RECT, FMA, SI, SJ>), dim3(blocks), dim3(kBlock), lds, stream, a); } while (0)
-  if (si == 4 && sj == 4) GO(4, 4);
-  else if (si == 2 && sj == 4) GO(2, 4);
-  else if (si == 2 && sj == 2) GO(2, 2);
-  else if (si == 1 && sj == 4) GO(1, 4);
-  else if (si == 1 && sj == 1) GO(1, 1);
-  else return hipErrorInvalidValue;
-#undef GO
-  return hipGetLastError();
-}
+struct CubicGradKernel {
+  static constexpr const char* name = "k_cubic_grad";
+  template <typename T, int N> using Args = CubicGradArgs<T, N>;
+  template <typename T, int N, bool RECT, bool FMA, int SI, int SJ>
+  static auto kernel() { return &k_cubic_grad<T, N, RECT, FMA, SI, SJ>; }
+};
 
 template <typename T, int N>
 static hipError_t cubic_grad_launch_fused(const GridDesc& g, const T* const* obs, T* out, T* const* grad, size_t npts,
                                           unsigned long long* first_bad, hipStream_t stream) {
   CubicGradArgs<T, N> a;
-  a.bricks = static_cast<const T*>(g.bricks);
-  {
-    unsigned nb[2];
-    size_t bytes = 0;
-    cubic_tile_geometry(g, g.brick_step[0], g.brick_step[1], nb, &bytes);
-    a.table_bytes = (unsigned)bytes;  // < 4 GiB by construction (maybe_build_cubic_tiles)
-  }
   a.out = out;
-  a.first_bad = first_bad;
-  a.npts = npts;
-  a.linearize = g.linearize;
   for (int d = 0; d < N; ++d) {
     a.obs[d] = obs[d];
     a.grad[d] = grad[d];
-    a.start[d] = (T)g.start[d];
-    a.step[d] = (T)g.step[d];
-    a.n[d] = g.n[d];
-    a.plane_stride[d] = 0;
   }
-  a.nbj = g.brick_nb[1];
-  if (N == 3) a.plane_stride[2] = g.brick_nb[0] * g.brick_nb[1] * 16u;  // table[k][bi][bj][16]
-  const bool dma = g.brick_step[0] == 1 && g.brick_step[1] == 1;  // cubic_brick.h::cubic_dma
-  size_t lds = dma ? (size_t)(kBlock / 64) * cubic_dma_image<T>() : (size_t)kBlock * kCubRow * (sizeof(T) > 4 ? sizeof(T) : 4);
-  a.ax.use_lds = 0;
-  a.ax.image = nullptr;
-  a.ax.image_bytes = 0;
-  if (g.kind == kRectilinear) lds += fill_axis_args<T, N>(g, a.ax);
-  const unsigned blocks = grid_blocks(npts, 1, g.cfg);
-  if (g.kind == kRegular)
-    return g.fma ? cubic_grad_launch_steps<T, N, false, true>(g, a, lds, blocks, stream)
-                 : cubic_grad_launch_steps<T, N, false, false>(g, a, lds, blocks, stream);
-  return g.fma ? cubic_grad_launch_steps<T, N, true, true>(g, a, lds, blocks, stream)
-               : cubic_grad_launch_steps<T, N, true, false>(g, a, lds, blocks, stream);
+  return cubic_cell_launch<CubicGradKernel, T, N>(g, a, npts, first_bad, grid_blocks(npts, 1, g.cfg), stream);
 }
 
 template <typename T>

@@ -86,18 +86,10 @@ __global__ void __launch_bounds__(kBlock) k_lattice_axes(const LatticeAxesArgs<T
         r.t = (x - index_zero_loc) / p.step;
       } else {
         ok &= floc != (T)-9223372036854775808.0;  // `- 1` would overflow isize: the reference panics
-        const T n = (T)p.n;
-        r.loc = clamp_loc<T>(floc - (T)1, p.n - 4);  // multicubic/regular.rs:440-442
-        int sat;
-        bool outside;
-        if (floc < (T)0) { sat = kSatLow; outside = true; }  // regular.rs:445-466 (see k_cubic_regular)
-        else if (floc == (T)0) { sat = kSatLow; outside = false; }
-        else if (floc > n - (T)2) { sat = kSatHigh; outside = true; }
-        else if (floc == n - (T)2) { sat = kSatHigh; outside = false; }
-        else { sat = kSatNone; outside = false; }
-        const T index_one_loc = mul_add<false>(p.step, (T)(r.loc + 1), p.start);  // regular.rs:356-360 — never fused
+        INTERPN_CUBIC_CLASS(floc, p.start, p.step, p.n)  // multicubic/regular.rs:440-466, :356-360
+        r.loc = l;
         const T t = (x - index_one_loc) / p.step;
-        r.tt = sat == kSatLow ? -t : (sat == kSatHigh ? t - (T)1 : t);
+        r.tt = INTERPN_CUBIC_TT(t);
         r.cls = sat | ((outside && a.linearize) ? 4 : 0);
       }
       lattice_report<T>(a, c, p, ok);

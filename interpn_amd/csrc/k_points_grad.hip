@@ -1,8 +1,10 @@
 // Host side of the point-major value-and-gradient evaluation (points_grad.h): whether a fused kernel takes a handle,
-// their launchers (the multilinear one through linear_cell_launch.h, the multicubic one with the dispatch of
-// k_cubic_grad.hip), the gradient-row store form, and the launcher of the split path's interleaving kernel.
+// their launchers (the multilinear one through linear_cell_launch.h, the multicubic one through cubic_cell_launch.h:
+// each sets its kernel's own arguments), the gradient-row store form, and the launcher of the split path's interleaving
+// kernel.
 #include <cstdlib>
 
+#include "cubic_cell_launch.h"
 #include "linear_cell_launch.h"
 #include "points_grad.h"
 
@@ -11,10 +13,10 @@ namespace interpn {
 bool points_fused_applies(const GridDesc& g);  // k_linear_points.hip
 
 // Multilinear: where k_linear_points runs (points_fused_applies), rows of up to kPointsGradMaxStride elements.
-// Multicubic: where k_cubic_grad runs, the tiled table of a 2-D or 3-D handle.
+// Multicubic: where k_cubic_grad runs (cubic_grad_fused_applies), the tiled table of a 2-D or 3-D handle.
 bool points_grad_fused_applies(const GridDesc& g, size_t stride, size_t gstride) {
   if (g.method == kLinear) return points_fused_applies(g) && stride <= kPointsGradMaxStride && gstride <= kPointsGradMaxStride;
-  return g.method == kCubic && g.bricks && !g.cfg.force_generic && (g.ndims == 2 || g.ndims == 3);
+  return cubic_grad_fused_applies(g);
 }
 
 struct PointsGradKernel {
@@ -50,61 +52,25 @@ static hipError_t pg_launch_linear(const GridDesc& g, const T* pts, size_t strid
   return cell_launch<PointsGradKernel, T, N>(g, a, npts, first_bad, two, stream);
 }
 
-template <typename T, int N, bool RECT, bool FMA>
-static hipError_t pg_cubic_steps(const GridDesc& g, const CubicPointsGradArgs<T, N>& a, size_t lds, unsigned blocks, hipStream_t stream) {
-  const int si = g.brick_step[0], sj = g.brick_step[1];
-#define GO(SI, SJ) do { g.tag.set("k_cubic_points_grad", {N, RECT, FMA, SI, SJ}, 0b00110u); hipLaunchKernelGGL((k_cubic_points_grad<T, N, RECT, FMA, SI, SJ>), dim3(blocks), dim3(kBlock), lds, stream, a); } while (0)
-  if (si == 4 && sj == 4) GO(4, 4);
-  else if (si == 2 && sj == 4) GO(2, 4);
-  else if (si == 2 && sj == 2) GO(2, 2);
-  else if (si == 1 && sj == 4) GO(1, 4);
-  else if (si == 1 && sj == 1) GO(1, 1);
-  else return hipErrorInvalidValue;
-#undef GO
-  return hipGetLastError();
-}
+struct CubicPointsGradKernel {
+  static constexpr const char* name = "k_cubic_points_grad";
+  template <typename T, int N> using Args = CubicPointsGradArgs<T, N>;
+  template <typename T, int N, bool RECT, bool FMA, int SI, int SJ>
+  static auto kernel() { return &k_cubic_points_grad<T, N, RECT, FMA, SI, SJ>; }
+};
 
 template <typename T, int N>
 static hipError_t pg_launch_cubic(const GridDesc& g, const T* pts, size_t stride, T* out, T* grad, size_t gstride, size_t npts,
                                   unsigned long long* first_bad, hipStream_t stream) {
   CubicPointsGradArgs<T, N> a;
-  a.bricks = static_cast<const T*>(g.bricks);
-  {
-    unsigned nb[2];
-    size_t bytes = 0;
-    cubic_tile_geometry(g, g.brick_step[0], g.brick_step[1], nb, &bytes);
-    a.table_bytes = (unsigned)bytes;  // < 4 GiB by construction (maybe_build_cubic_tiles)
-  }
   a.pts = pts;
   a.stride = stride;
   a.out = out;
   a.grad = grad;
   a.gstride = gstride;
-  a.first_bad = first_bad;
-  a.npts = npts;
-  a.linearize = g.linearize;
   a.vec2_load = N == 2 && stride == 2 && aligned2<T>(pts);
   a.vec2_store = N == 2 && gstride == 2 && aligned2<T>(grad);
-  for (int d = 0; d < N; ++d) {
-    a.start[d] = (T)g.start[d];
-    a.step[d] = (T)g.step[d];
-    a.n[d] = g.n[d];
-    a.plane_stride[d] = 0;
-  }
-  a.nbj = g.brick_nb[1];
-  if (N == 3) a.plane_stride[2] = g.brick_nb[0] * g.brick_nb[1] * 16u;  // table[k][bi][bj][16]
-  const bool dma = g.brick_step[0] == 1 && g.brick_step[1] == 1;  // cubic_brick.h::cubic_dma
-  size_t lds = dma ? (size_t)(kBlock / 64) * cubic_dma_image<T>() : (size_t)kBlock * kCubRow * (sizeof(T) > 4 ? sizeof(T) : 4);
-  a.ax.use_lds = 0;
-  a.ax.image = nullptr;
-  a.ax.image_bytes = 0;
-  if (g.kind == kRectilinear) lds += fill_axis_args<T, N>(g, a.ax);
-  const unsigned blocks = grid_blocks(npts, 1, g.cfg);
-  if (g.kind == kRegular)
-    return g.fma ? pg_cubic_steps<T, N, false, true>(g, a, lds, blocks, stream)
-                 : pg_cubic_steps<T, N, false, false>(g, a, lds, blocks, stream);
-  return g.fma ? pg_cubic_steps<T, N, true, true>(g, a, lds, blocks, stream)
-               : pg_cubic_steps<T, N, true, false>(g, a, lds, blocks, stream);
+  return cubic_cell_launch<CubicPointsGradKernel, T, N>(g, a, npts, first_bad, grid_blocks(npts, 1, g.cfg), stream);
 }
 
 template <typename T>

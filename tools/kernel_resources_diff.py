@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Compare the kernel resources of two builds of the same translation units, per instantiation.
 
-    for u in k_linear_grad k_linear_points k_points_grad; do
+    for u in UNIT...; do                   (the translation units under comparison, e.g. k_cubic_grad k_points_grad)
       hipcc <the Makefile's CXXFLAGS> -Rpass-analysis=kernel-resource-usage --cuda-device-only -S $u.hip -o DIR/$u.s 2> DIR/$u.remarks
     done                                   (once in each tree: DIR = before/, after/)
-    python tools/kernel_resources_diff.py before after k_linear_grad k_linear_points k_points_grad > table.csv
+    python tools/kernel_resources_diff.py before after UNIT... > table.csv
 
 Writes one CSV row per kernel and, to stderr, a summary per unit.  Exit status 1 if an instantiation gained scratch or
 AGPRs, changed its LDS size, or sits on a lower occupancy step than before (512 VGPRs per SIMD, allocated in granules of 8,
