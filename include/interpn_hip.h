@@ -593,6 +593,48 @@ int interpn_hip_fields_get_option(const interpn_hip_fields* fields, const char* 
 int interpn_hip_fields_layout(size_t elem_size, size_t ndims, const size_t* dims, size_t nfields, int* fields_per_line,
                               size_t* lines_per_point, size_t* table_bytes);
 
+/* Point-major field sets — the points as ONE array of shape (npoints, N), the results as ONE array of shape (npoints, K):
+ * positions or ray samples in, a velocity or an RGBA per point out, without a transpose on either side.
+ *
+ * Definition  coordinate d of point i is pts[i * point_stride + d] (point_stride >= ndims, in ELEMENTS; elements d >= ndims
+ *           of a row are never read, the last row's may not exist); field f of point i goes to out[i * out_stride + f]
+ *           (out_stride >= nfields; elements f >= nfields of a row are never written).  `pts` and `out` must not overlap.
+ *           Every result has the bits of interpn_hip_fields_eval_device on the de-interleaved columns.
+ * Paths     FUSED (sets with the fused table: multilinear N = 2, 3): one launch of interpn::k_linear_fields_points on
+ *           that table — k_linear_fields' statements between a row load (dense rows: the wave's span through LDS; any other
+ *           stride: element loads) and a row store (the wave's results staged as a [64][8] tile in LDS and stored as
+ *           contiguous runs: one run of 64 K elements per wave where out_stride == K <= 8).  No scratch, never allocates,
+ *           can be captured into a graph.
+ *           SPLIT (everything else: cubic, nearest, N = 1, N >= 4, sets without the table, "fused" = 0): per slice
+ *           interpn::k_split_points de-interleaves the rows into scratch, the column form evaluates them into K scratch
+ *           rows (fused or per field by the option "fused" and its rule), interpn::k_join_fields writes the caller's rows.
+ *           One scratch block, from the first field's handle, holds a slice: (N + K) arrays within 64 MiB together, 256
+ *           points at least.  Under graph capture or with INTERPN_HIP_EVAL_NO_ALLOC only reserved blocks are used
+ *           (INTERPN_HIP_ERR_OUT_OF_MEMORY without one); interpn_hip_fields_reserve_points provides them.
+ * Options   "points_path" = -1 automatic (fused wherever the set has the table and "fused" is not 0),
+ *           1 fused or INTERPN_HIP_ERR_UNSUPPORTED, 2 split.  Read-only "last_points_path" (INTERPN_HIP_FIELDS_POINTS_PATH_*;
+ *           -1 before any).  "points_slice" (testing): points per slice of the split path.  interpn_hip_fields_kernel_name
+ *           reports "interpn::k_linear_fields_points<double, 3, false, true>" after a fused call.
+ * Checks    before any device work, in this order: fields NULL; point_stride < ndims, out_stride < nfields:
+ *           INTERPN_HIP_ERR_INVALID_ARGUMENT; npoints == 0: INTERPN_HIP_OK whatever the pointers are; pts or out NULL, or a
+ *           block whose bytes do not fit size_t: INTERPN_HIP_ERR_INVALID_ARGUMENT; "points_path" = 1 without the table:
+ *           INTERPN_HIP_ERR_UNSUPPORTED.
+ * Failing   device form: interpn_hip_fields_finish reports the first failing point of the whole call, on every path.  Host
+ * points    form: the set's status; exactly rows [0, i) are written, their first K elements only, everything else is left
+ *           as it was. */
+enum { INTERPN_HIP_FIELDS_POINTS_PATH_FUSED = 0, INTERPN_HIP_FIELDS_POINTS_PATH_SPLIT = 1 };
+/* Asynchronous on `stream`; `pts`, `out`: device.  `flags`: INTERPN_HIP_EVAL_NO_ALLOC.  *path_taken (may be NULL). */
+int interpn_hip_fields_eval_points_device(interpn_hip_fields* fields, const void* pts, size_t point_stride, size_t npoints,
+                                          void* out, size_t out_stride, void* stream, unsigned flags, int* path_taken);
+/* The same on host arrays, synchronous: chunks of 2 Mi points (option "host_chunk"), a chunk's rows uploaded with one copy,
+ * only the first K elements of the rows in front of a failing point downloaded. */
+int interpn_hip_fields_eval_points_host(interpn_hip_fields* fields, const void* pts, size_t point_stride, size_t npoints,
+                                        void* out, size_t out_stride);
+/* Scratch blocks for split-path evaluations of up to `npoints` points on up to `nstreams` concurrent streams (blocks of
+ * the first field's handle; per-field evaluations of large batches may want interpn_hip_reserve on the handles' paths as
+ * well, which a set does not expose: under NO_ALLOC they evaluate in place). */
+int interpn_hip_fields_reserve_points(interpn_hip_fields* fields, size_t npoints, int nstreams);
+
 /* ------------------------------------------------------------------------------------------
  * Lattice evaluation — the points are the tensor product of N coordinate vectors, one per axis: re-gridding,
  * RegularGridInterpolator on a meshgrid, resampling a volume, refining a table.  The caller passes the N vectors

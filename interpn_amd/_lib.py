@@ -34,6 +34,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 FLAVOUR_FMA, FLAVOUR_NO_FMA = 0x100, 0x200  # OR-ed into `method` of interpn_hip_create_*
 PATH_IN_PLACE, PATH_BINNED, PATH_SWEEP = 0, 1, 2
 FIELDS_PATH_FUSED, FIELDS_PATH_PER_FIELD = 0, 1  # interpn_hip_fields_eval_device
+FIELDS_POINTS_PATHS = {0: "fused", 1: "split"}  # interpn_hip_fields_eval_points_device
 LATTICE_PATH_FUSED, LATTICE_PATH_EXPANDED = 0, 1  # interpn_hip_eval_lattice_device
 LATTICE_PATHS = {LATTICE_PATH_FUSED: "fused", LATTICE_PATH_EXPANDED: "expanded"}
 POINTS_PATHS = {0: "fused", 1: "split", 2: "direct"}  # interpn_hip_eval_points_device
@@ -181,6 +182,10 @@ def load() -> ctypes.CDLL:
     lib.interpn_hip_fields_get_option.argtypes = [c_void_p, c_char_p, POINTER(ctypes.c_longlong)]
     lib.interpn_hip_fields_layout.argtypes = [c_size_t, c_size_t, POINTER(c_size_t), c_size_t, POINTER(c_int), POINTER(c_size_t),
                                               POINTER(c_size_t)]
+    lib.interpn_hip_fields_eval_points_device.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p,
+                                                          ctypes.c_uint, POINTER(c_int)]
+    lib.interpn_hip_fields_eval_points_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t]
+    lib.interpn_hip_fields_reserve_points.argtypes = [c_void_p, c_size_t, c_int]
     lib.interpn_hip_eval_lattice_device.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_void_p,
                                                     ctypes.c_uint, POINTER(c_int)]
     lib.interpn_hip_eval_lattice_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p,

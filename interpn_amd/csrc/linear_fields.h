@@ -84,89 +84,112 @@ __device__ __forceinline__ T fields_cross_level(T r, T t, int piece) {
   return fields_node<FMA, T>(t, upper ? other : r, upper ? r : other);
 }
 
+// What k_linear_fields and k_linear_fields_points (linear_fields_points.h) do between their own coordinate loads and result
+// stores, as statements expanded in place (macros for the reason linear_cell.h gives: an inlined function is optimised on
+// its own first, and the kernel built from it is not the kernel built from the statements).  The template parameters T, N,
+// RECT, FMA, the layout L = FieldsLayout<T, N>, the 16-byte piece type V and the kernel's arguments `a` (table, groups,
+// cstride, start, step, n, ax, first_bad) are the kernels' own.
+//
+// INTERPN_FIELDS_PROLOGUE(WAVE_LDS)  declares smem_raw, axbase (the rectilinear axes: LDS or L2), wave, lane, wlds = the
+//     wave's WAVE_LDS bytes of LDS, s_line and s_t at its start, piece, psub.
+#define INTERPN_FIELDS_PROLOGUE(WAVE_LDS) \
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];    \
+  unsigned lds_axes = 0;                                                      \
+  const unsigned char* axbase = nullptr;                                      \
+  if constexpr (RECT) {                                                       \
+    axbase = a.ax.image;                                                      \
+    if (a.ax.use_lds) {                                                       \
+      stage_axes<T, N>(a.ax, smem_raw);                                       \
+      lds_axes = (a.ax.image_bytes + 15u) & ~15u;                             \
+      axbase = smem_raw;                                                      \
+    }                                                                         \
+  }                                                                           \
+  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);  \
+  unsigned char* wlds = smem_raw + lds_axes + (unsigned)wave * (WAVE_LDS);    \
+  lds_u32* s_line = reinterpret_cast<lds_u32*>(wlds);                         \
+  T* s_t = reinterpret_cast<T*>(wlds + 256);                                  \
+  const int piece = lane & 7, psub = lane >> 3;
+
+// INTERPN_FIELDS_LOCATE(X, LIVE, INDEX)  the point of this lane: X is its coordinate along `d` (an expression in d; lanes
+//     behind the batch give a harmless one), a LIVE point the grid cannot place reports INDEX.  Shares {first line of the
+//     cell, t[N]} of the wave's 64 points through s_line / s_t and declares lines[8], the lines this lane fetches pieces of.
+#define INTERPN_FIELDS_LOCATE(X, LIVE, INDEX) \
+  T t[N];                                                                                                        \
+  unsigned line = 0;                                                                                             \
+  bool ok = true;                                                                                                \
+  _Pragma("unroll")                                                                                              \
+  for (int d = 0; d < N; ++d) {                                                                                  \
+    int loc;                                                                                                     \
+    if constexpr (RECT) {                                                                                        \
+      const T x = (X);                                                                                           \
+      const Axis<T> ax = make_axis<T, N>(a.ax, axbase, d);                                                       \
+      T x0, x1;                                                                                                  \
+      loc = axis_cell<T>(ax, x, &x0, &x1);  /* rectilinear.rs:353-370, :310-311 */                               \
+      const T step = x1 - x0;                                                                                    \
+      t[d] = (x - x0) / step;               /* rectilinear.rs:310-313 */                                         \
+    } else {                                                                                                     \
+      const T x = (X);                                                                                           \
+      T floc;                                                                                                    \
+      ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);  /* regular.rs:415-418 */                          \
+      loc = clamp_loc<T>(floc, a.n[d] - 2);                    /* regular.rs:420-422 */                          \
+      const T index_zero_loc = mul_add<FMA>(a.step[d], (T)loc, a.start[d]);  /* regular.rs:334-339 */            \
+      t[d] = (x - index_zero_loc) / a.step[d];                                                                   \
+    }                                                                                                            \
+    line += (unsigned)loc * a.cstride[d];                                                                        \
+  }                                                                                                              \
+  if (!ok && (LIVE)) atomicMin(a.first_bad, (unsigned long long)(INDEX));                                        \
+  s_line[lane] = line;                                                                                           \
+  _Pragma("unroll")                                                                                              \
+  for (int d = 0; d < N; ++d) s_t[d * 64 + lane] = t[d];                                                         \
+  wave_sync();                                                                                                   \
+  unsigned lines[8];                                                                                             \
+  _Pragma("unroll")                                                                                              \
+  for (int j = 0; j < 8; ++j) lines[j] = s_line[j * 8 + psub];
+
+// INTERPN_FIELDS_GROUP(G, DST)  line group G of the wave's 64 points: 8 lanes x 16 bytes fetch one point's line, every
+//     field's tree runs in the reference's order, and the lane that ends up with field `fl` of the line for point `p` of
+//     the wave stores it to DST (an LDS lvalue in fl and p).
+#define INTERPN_FIELDS_GROUP(G, DST) \
+  V v[8];                                                                                                                 \
+  _Pragma("unroll")                                                                                                       \
+  for (int j = 0; j < 8; ++j)                                                                                             \
+    v[j] = *reinterpret_cast<const V*>(a.table + ((size_t)lines[j] + (G)) * L::kLineBytes + (unsigned)piece * 16u);       \
+  _Pragma("unroll")                                                                                                       \
+  for (int j = 0; j < 8; ++j) {                                                                                           \
+    const int p = j * 8 + psub;                                                                                           \
+    T tt[N];                                                                                                              \
+    _Pragma("unroll")                                                                                                     \
+    for (int d = 0; d < N; ++d) tt[d] = s_t[d * 64 + p];                                                                  \
+    T r;                                                                                                                  \
+    if constexpr (L::LB == 1) {                                                                                           \
+      r = fields_node<FMA, T>(tt[0], v[j][0], v[j][1]);                                                                   \
+    } else {                                                                                                              \
+      const T r0 = fields_node<FMA, T>(tt[0], v[j][0], v[j][1]);                                                          \
+      const T r1 = fields_node<FMA, T>(tt[0], v[j][2], v[j][3]);                                                          \
+      r = fields_node<FMA, T>(tt[1], r0, r1);                                                                             \
+    }                                                                                                                     \
+    if constexpr (L::XB >= 1) r = fields_cross_level<0, FMA, T>(r, tt[L::LB], piece);                                     \
+    if constexpr (L::XB >= 2) r = fields_cross_level<1, FMA, T>(r, tt[L::LB + 1], piece);                                 \
+    const int fl = piece >> L::XB;                                                                                        \
+    if ((piece & ((1 << L::XB) - 1)) == 0) DST = r;                                                                       \
+  }
+
 template <typename T, int N, bool RECT, bool FMA>
 __global__ void __launch_bounds__(kBlock) k_linear_fields(const FieldsArgs<T, N> a) {
   typedef FieldsLayout<T, N> L;
   typedef T V __attribute__((ext_vector_type(L::EPP)));
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  unsigned lds_axes = 0;
-  const unsigned char* axbase = nullptr;
-  if constexpr (RECT) {
-    axbase = a.ax.image;
-    if (a.ax.use_lds) {
-      stage_axes<T, N>(a.ax, smem_raw);
-      lds_axes = (a.ax.image_bytes + 15u) & ~15u;
-      axbase = smem_raw;
-    }
-  }
-  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
-  unsigned char* wlds = smem_raw + lds_axes + (unsigned)wave * L::kWaveLds;
-  lds_u32* s_line = reinterpret_cast<lds_u32*>(wlds);
-  T* s_t = reinterpret_cast<T*>(wlds + 256);
+  INTERPN_FIELDS_PROLOGUE(L::kWaveLds);
   T* s_res = s_t + N * 64;
-  const int piece = lane & 7, psub = lane >> 3;
 
   // whole workgroups iterate together: every lane of a wave stays active (the exchanges below need it);
   // lanes behind the batch evaluate a harmless coordinate and only their stores are masked
   for (size_t base = (size_t)blockIdx.x * kBlock; base < a.npts; base += (size_t)gridDim.x * kBlock) {
     const size_t i = base + threadIdx.x;
     const bool live = i < a.npts;
-    T t[N];
-    unsigned line = 0;
-    bool ok = true;
-#pragma unroll
-    for (int d = 0; d < N; ++d) {
-      int loc;
-      if constexpr (RECT) {
-        const T x = live ? stream_load(a.obs[d] + i) : (T)0;
-        const Axis<T> ax = make_axis<T, N>(a.ax, axbase, d);
-        T x0, x1;
-        loc = axis_cell<T>(ax, x, &x0, &x1);  // rectilinear.rs:353-370, :310-311
-        const T step = x1 - x0;
-        t[d] = (x - x0) / step;               // rectilinear.rs:310-313
-      } else {
-        const T x = live ? stream_load(a.obs[d] + i) : a.start[d];
-        T floc;
-        ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);  // regular.rs:415-418
-        loc = clamp_loc<T>(floc, a.n[d] - 2);                    // regular.rs:420-422
-        const T index_zero_loc = mul_add<FMA>(a.step[d], (T)loc, a.start[d]);  // regular.rs:334-339
-        t[d] = (x - index_zero_loc) / a.step[d];
-      }
-      line += (unsigned)loc * a.cstride[d];
-    }
-    if (!ok && live) atomicMin(a.first_bad, (unsigned long long)i);
-    s_line[lane] = line;
-#pragma unroll
-    for (int d = 0; d < N; ++d) s_t[d * 64 + lane] = t[d];
-    wave_sync();
-
-    unsigned lines[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) lines[j] = s_line[j * 8 + psub];
+    INTERPN_FIELDS_LOCATE(live ? stream_load(a.obs[d] + i) : (RECT ? (T)0 : a.start[d]), live, i);
     const size_t wbase = base + (size_t)wave * 64;
     for (unsigned g = 0; g < a.groups; ++g) {
-      V v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        v[j] = *reinterpret_cast<const V*>(a.table + ((size_t)lines[j] + g) * L::kLineBytes + (unsigned)piece * 16u);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int p = j * 8 + psub;
-        T tt[N];
-#pragma unroll
-        for (int d = 0; d < N; ++d) tt[d] = s_t[d * 64 + p];
-        T r;
-        if constexpr (L::LB == 1) {
-          r = fields_node<FMA, T>(tt[0], v[j][0], v[j][1]);
-        } else {
-          const T r0 = fields_node<FMA, T>(tt[0], v[j][0], v[j][1]);
-          const T r1 = fields_node<FMA, T>(tt[0], v[j][2], v[j][3]);
-          r = fields_node<FMA, T>(tt[1], r0, r1);
-        }
-        if constexpr (L::XB >= 1) r = fields_cross_level<0, FMA, T>(r, tt[L::LB], piece);
-        if constexpr (L::XB >= 2) r = fields_cross_level<1, FMA, T>(r, tt[L::LB + 1], piece);
-        if ((piece & ((1 << L::XB) - 1)) == 0) s_res[(piece >> L::XB) * 64 + p] = r;
-      }
+      INTERPN_FIELDS_GROUP(g, s_res[fl * 64 + p]);
       wave_sync();
 #pragma unroll
       for (int fl = 0; fl < L::P; ++fl) {

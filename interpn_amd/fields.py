@@ -72,6 +72,7 @@ class Fields:
         self._keepalive = keepalive
         self._pending_streams = {}
         self.last_path = None
+        self.last_points_path = None
 
     # -- construction ---------------------------------------------------------------------
     @classmethod
@@ -206,6 +207,124 @@ class Fields:
         self.eval_device_ptrs([t.data_ptr() for t in obs], out.data_ptr(), max(out.stride(0), n) if n else 0, n, raw, no_alloc)
         self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
         return out
+
+    # -- point-major evaluation: (n, N) points in, (n, K) values out -------------------------
+    def reserve_points(self, npoints: int, nstreams: int = 1) -> None:
+        """Pre-allocate the scratch that split-path point-major evaluations of up to `npoints` points on up to `nstreams`
+        concurrent streams need (`interpn_hip_fields_reserve_points`); afterwards they work with `no_alloc=True` and
+        under graph capture.  The fused kernel (sets with the fused table) needs none."""
+        _lib.raise_for_status(_lib.load().interpn_hip_fields_reserve_points(self._h, int(npoints), int(nstreams)))
+
+    def _took_points(self) -> None:
+        self.last_points_path = _lib.FIELDS_POINTS_PATHS.get(self.get_option("last_points_path"))
+        self._took()
+
+    def eval_points_host(self, pts, out=None) -> np.ndarray:
+        """Every field at the rows of a host array of shape `(n, N)` or `(..., N)` (synchronous;
+        `interpn_hip_fields_eval_points_host`): an `(n, K)` or `(..., K)` array whose element `[i, f]` has the bits of
+        `eval_host(columns)[f, i]`.  A C-contiguous array, or a 2-D view whose last axis is unit-stride and whose row
+        stride is a whole number of elements (`buf[:, :3]` of an `(n, 4)` array), is taken as it is; anything else is
+        copied once.  `out` may have any row stride >= K with unit-stride rows; elements behind a row's first K are not
+        touched.  On "Unrepresentable coordinate value" exactly the rows in front of the failing point are written."""
+        if not isinstance(pts, np.ndarray):
+            raise TypeError(f"argument 'pts': expected a numpy array, got {type(pts).__name__}")
+        if pts.dtype != self.dtype:
+            raise TypeError(f"argument 'pts': expected dtype {self.dtype.name}, got {pts.dtype.name}")
+        nd, k, item = self._ndims, self.nfields, self.dtype.itemsize
+        if pts.ndim < 1 or pts.shape[-1] != nd:
+            raise ValueError(f"argument 'pts': expected shape (..., {nd}), got {tuple(pts.shape)}")
+        lead = tuple(pts.shape[:-1])
+        if pts.ndim == 2 and (nd == 1 or pts.strides[1] == item) and (
+                pts.shape[0] <= 1 or (pts.strides[0] % item == 0 and pts.strides[0] >= nd * item)):
+            rows = pts
+        else:
+            rows = np.ascontiguousarray(pts).reshape(-1, nd)
+        n = rows.shape[0]
+        stride = rows.strides[0] // item if n > 1 else nd
+        if out is None:
+            out = np.zeros(lead + (k,), dtype=self.dtype)
+        if not isinstance(out, np.ndarray) or out.dtype != self.dtype:
+            raise TypeError(f"out: expected a numpy array of {self.dtype.name}")
+        if tuple(out.shape) != lead + (k,):
+            raise ValueError(f"out: expected shape {lead + (k,)}, got {tuple(out.shape)}")
+        if not out.flags.writeable:
+            raise ValueError("out: array is read-only")
+        if out.ndim == 2:
+            if n and k > 1 and out.strides[1] != item:
+                raise ValueError("out: every row must be contiguous (unit stride along the last axis)")
+            if n > 1 and (out.strides[0] % item or out.strides[0] < k * item):
+                raise ValueError(f"out: the row stride must be a whole number of elements, at least {k}")
+            ostride = out.strides[0] // item if n > 1 else k
+        else:
+            if not out.flags.c_contiguous:
+                raise ValueError("out: expected a C-contiguous array, or a 2-D array with contiguous rows")
+            ostride = k
+        st = _lib.load().interpn_hip_fields_eval_points_host(self._h, c_void_p(rows.ctypes.data), stride, n, c_void_p(out.ctypes.data),
+                                                            ostride)
+        self._took_points()
+        _lib.raise_for_status(st)
+        return out
+
+    def eval_points_tensors(self, pts, out=None, stream=None, no_alloc: bool = False):
+        """The same on a torch CUDA tensor (asynchronous on torch's current stream unless given;
+        `interpn_hip_fields_eval_points_device`): no `pts.T.contiguous()` in front and no transpose of the result behind.
+        `pts` and `out` must not overlap.  Sets with the fused table run one kernel, which can be captured into a graph;
+        `last_points_path` says which path ran; `finish()` synchronises and surfaces "Unrepresentable coordinate value"."""
+        import torch
+
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        nd, k = self._ndims, self.nfields
+        if not (hasattr(pts, "is_cuda") and pts.is_cuda and pts.dtype == want):
+            raise TypeError(f"pts: expected a {want} CUDA tensor of shape (..., {nd})")
+        if pts.dim() < 1 or pts.shape[-1] != nd:
+            raise ValueError(f"pts: expected shape (..., {nd}), got {tuple(pts.shape)}")
+        dev = self.device()
+        if pts.device.index not in (None, dev):
+            raise ValueError(f"pts is on {pts.device} but this set lives on cuda:{dev}")
+        lead = tuple(pts.shape[:-1])
+        if pts.dim() == 2 and (nd == 1 or pts.stride(1) == 1) and (pts.shape[0] <= 1 or pts.stride(0) >= nd):
+            rows = pts
+        else:
+            rows = pts.contiguous().reshape(-1, nd)
+        n = int(rows.shape[0])
+        stride = int(rows.stride(0)) if n > 1 else nd
+        if out is None:
+            out = torch.empty(lead + (k,), dtype=want, device=torch.device("cuda", dev))
+        if not (hasattr(out, "is_cuda") and out.is_cuda and out.dtype == want):
+            raise TypeError(f"out: expected a {want} CUDA tensor")
+        if tuple(out.shape) != lead + (k,):
+            raise ValueError(f"out: expected shape {lead + (k,)}, got {tuple(out.shape)}")
+        if out.device.index not in (None, dev):
+            raise ValueError(f"out is on {out.device} but this set lives on cuda:{dev}")
+        if out.dim() == 2:
+            if n and k > 1 and out.stride(1) != 1:
+                raise ValueError("out: every row must be contiguous (unit stride along the last axis)")
+            if n > 1 and out.stride(0) < k:
+                raise ValueError(f"out: the row stride must be at least {k}")
+            ostride = int(out.stride(0)) if n > 1 else k
+        else:
+            if not out.is_contiguous():
+                raise ValueError("out: expected a contiguous tensor, or a 2-D tensor with contiguous rows")
+            ostride = k
+        owner = torch.cuda.current_stream(dev) if stream is None else stream
+        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        path = ctypes.c_int(0)
+        st = _lib.load().interpn_hip_fields_eval_points_device(self._h, c_void_p(rows.data_ptr()), stride, n, c_void_p(out.data_ptr()),
+                                                              ostride, c_void_p(int(raw)), _lib.EVAL_NO_ALLOC if no_alloc else 0,
+                                                              ctypes.byref(path))
+        _lib.raise_for_status(st)
+        if n:
+            self._took_points()
+        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        return out
+
+    def eval_points(self, pts, out=None, **kwargs):
+        """`eval_points_tensors` for a torch tensor, `eval_points_host` for a numpy array."""
+        if _is_tensor(pts):
+            return self.eval_points_tensors(pts, out, **kwargs)
+        if kwargs:
+            raise TypeError(f"eval_points on a host array takes no {sorted(kwargs)}")
+        return self.eval_points_host(pts, out)
 
     def finish(self, stream=None) -> None:
         """Wait for the evaluations enqueued since the last finish; AssertionError("Unrepresentable coordinate
@@ -347,3 +466,90 @@ def interpn_fields(obs, grids, vals, *, method="linear", field_axis: int = 0, ou
             out[...] = res
         return out
     return res.contiguous() if on_device else np.ascontiguousarray(res)
+
+
+def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, linearize_extrapolation: bool = True,
+                          assume_regular: bool = False, check_bounds: bool = False, bounds_atol: float = 1e-8):
+    """scipy's `interpn(points, values, xi)` with trailing value dimensions: `vals` of shape (*dims, K), `xi` of shape
+    (..., N) — a numpy array or a torch CUDA tensor — and a result of shape (..., K).  The rules are those of
+    `interpn_fields` (dtype from `vals`, exact-spacing regularity test); the points and the result keep their layout
+    (`Fields.eval_points`), and the value table is re-laid field-major once, as part of setting the fields up."""
+    from . import _check_regular, _is_cuda_tensor, raw
+
+    if method not in ("linear", "cubic", "nearest"):
+        raise ValueError(f"Unsupported interpolation configuration: {method}")
+    if not (isinstance(vals, np.ndarray) or _is_tensor(vals)):
+        raise TypeError("vals: expected a numpy array or a torch tensor with a trailing field axis")
+    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
+    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
+    if not (isinstance(xi, np.ndarray) or _is_tensor(xi)):
+        raise TypeError("xi: expected a numpy array or a torch tensor of shape (..., N)")
+    grids = [np.ascontiguousarray(np.asarray(g).ravel()).astype(dtype, copy=False) for g in grids]
+    nd = len(grids)
+    if len(vals.shape) != nd + 1:
+        raise ValueError(f"vals: expected shape (*dims, K) for {nd} grids, got {tuple(vals.shape)}")
+    if len(xi.shape) < 1 or int(xi.shape[-1]) != nd:
+        raise ValueError(f"xi: expected shape (..., {nd}), got {tuple(xi.shape)}")
+    nper = int(np.prod([g.size for g in grids], dtype=object))
+    k = int(vals.shape[-1])
+    if tuple(int(v) for v in vals.shape[:-1]) != tuple(g.size for g in grids) or k < 1:
+        raise ValueError(f"vals: expected {k} x {nper} values for grids of {[g.size for g in grids]}, got shape {tuple(vals.shape)}")
+    on_device = _is_cuda_tensor(xi)
+    want = str(xi.dtype).rsplit(".", 1)[-1]
+    if want != dtype.name:
+        raise TypeError(f"xi: expected dtype {dtype.name} (that of vals), got {want}")
+    rshape = tuple(int(v) for v in xi.shape[:-1]) + (k,)
+    if out is not None and tuple(out.shape) != rshape:
+        raise ValueError(f"out: expected shape {rshape}, got {tuple(out.shape)}")
+    if _is_tensor(xi) and not on_device:
+        raise TypeError("xi: expected a numpy array or a torch CUDA tensor")
+    # (*dims, K) -> (K, prod(dims)), once: set-up, not part of the pass over the points
+    vals = vals.reshape(nper, k).T
+    vals = (vals.contiguous() if _is_tensor(vals) else np.ascontiguousarray(vals)).reshape(k, nper)
+    regular = assume_regular or _check_regular(grids)
+    device = -1
+    if on_device:
+        import torch
+
+        device = xi.device.index if xi.device.index is not None else torch.cuda.current_device()
+    elif _is_tensor(vals):
+        vals = vals.cpu().numpy()
+    if regular:
+        dims = [g.size for g in grids]
+        starts = np.array([g[0] for g in grids], dtype=dtype)
+        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
+    sfx = "f64" if dtype == np.float64 else "f32"
+    if check_bounds and not on_device:
+        cols = [np.ascontiguousarray(xi[..., d].ravel()) for d in range(nd)]
+        outb = np.zeros(nd, dtype=bool)
+        if regular:
+            getattr(raw, f"check_bounds_regular_{sfx}")(dims, starts, steps, cols, bounds_atol, outb)
+        else:
+            getattr(raw, f"check_bounds_rectilinear_{sfx}")(grids, cols, bounds_atol, outb)
+        if any(outb):
+            raise ValueError("Observation points violate interpolator bounds")
+    if regular:
+        fs = Fields.regular(method, dims, starts, steps, vals, linearize_extrapolation=linearize_extrapolation, device=device,
+                            dtype=dtype)
+    else:
+        fs = Fields.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
+    try:
+        if on_device:
+            if check_bounds:  # the bounds are the grid's: any one field's interpolator checks them on the device
+                from .handle import Interpolator
+
+                one = (Interpolator.regular(method, dims, starts, steps, vals[0], device=device, dtype=dtype) if regular
+                       else Interpolator.rectilinear(method, grids, vals[0], device=device, dtype=dtype))
+                try:
+                    cols = [xi[..., d].reshape(-1).contiguous() for d in range(nd)]
+                    if one.check_bounds_tensors(cols, bounds_atol).any():
+                        raise ValueError("Observation points violate interpolator bounds")
+                finally:
+                    one.close()
+            res = fs.eval_points_tensors(xi, out)
+            fs.finish()
+        else:
+            res = fs.eval_points_host(xi, out)
+    finally:
+        fs.close()
+    return res
