@@ -699,6 +699,74 @@ int interpn_hip_lattice_plan(size_t elem_size, int method, size_t ndims, const s
                              int* path, size_t* lds_bytes, size_t* npoints);
 
 /* ------------------------------------------------------------------------------------------
+ * Field sets on a lattice — K fields of one grid re-gridded onto the tensor product of N coordinate vectors in one pass:
+ * resizing an (H, W, C) image or a (D, H, W, C) volume, re-gridding several variables of a simulation onto a finer mesh,
+ * refining a table of K quantities.  `axes`, `axis_lens`, `naxes` as for interpn_hip_eval_lattice_device.
+ *
+ * Layouts   INTERPN_HIP_FIELDS_LATTICE_FIELD_MAJOR: out[f * out_stride + p], out_stride >= prod(axis_lens) — shape (K, *m);
+ *           INTERPN_HIP_FIELDS_LATTICE_FIELDS_LAST: out[p * out_stride + f], out_stride >= K — shape (*m, K), the
+ *           channel-last layout; p is the lattice index in C order, strides in ELEMENTS.  Nothing is written at f >= K,
+ *           behind a row's first K elements, or between two fields' blocks.  `out` must not overlap the axes.
+ * Contract  field f of every result has the bits of interpn_hip_eval_lattice_device on the handle of field f alone, on
+ *           both paths, in both fma flavours, and therefore the reference's.
+ * Paths     FUSED (multilinear and multicubic, N = 2 or 3, regular and rectilinear, f64 and f32, grids that 32 bits index):
+ *           ONE launch of interpn::k_lattice_axes for all K fields (the records do not depend on the field), then ONE launch
+ *           of interpn::k_lattice_fields_rows on the set's field-major `vals` — no re-laid table, so it is the one-pass
+ *           multicubic form of a set as well.  A wave owns a row and processes the fields in groups of G: G LDS lines (dims
+ *           0..N-2 of each field reduced at every grid column of the last axis), then per output the last axis's record once
+ *           and one node per field.  Fields-last results leave through a [64][G] LDS tile as contiguous runs (one run of
+ *           64 K elements per wave and chunk where out_stride == K == G).  G = the largest g <= min(K, 8) with
+ *           4 * (g * line + tile(g)) within the LDS budget of interpn_hip_eval_lattice_device ("axis_lds_kb"), line =
+ *           n_{N-1} elements rounded up to 16 bytes, tile(g) = 64 * (g | 1) elements rounded up to 16 bytes for
+ *           fields-last and 0 for field-major results; K > G: ceil(K / G) passes per row.  Takes a records block of the
+ *           FIRST field's handle under the rules of interpn_hip_eval_lattice_device; capturable after
+ *           interpn_hip_fields_reserve_lattice; builds none of the handles' deferred tables.
+ *           PER_FIELD (everything else: nearest, N = 1, N >= 4, last axes whose line does not fit, "lattice" = 0, grids 32
+ *           bits do not index, "force_generic"): K calls of interpn_hip_eval_lattice_device's path through the K handles.
+ *           Field-major results go straight into the caller's rows; fields-last results go, per slice of whole leading-axis
+ *           indices (K rows within 64 MiB together, one index at least; option "points_slice" = points, for tests), into
+ *           scratch rows of the first handle and through interpn::k_join_fields.
+ * Options   "lattice" and "axis_lds_kb" (forwarded to the K handles; the fused path reads the first one's).  "lattice" = 1:
+ *           fused wherever covered and G >= 1; -1 automatic: the rules of interpn_hip_eval_lattice_device and G >= 1
+ *           (measured, DESIGN.md section 16: no further rule for short runs per point).  Read-only "last_lattice_path"
+ *           (INTERPN_HIP_FIELDS_LATTICE_PATH_*; -1 before any) and "last_lattice_group" (G of the last fused evaluation).
+ *           interpn_hip_fields_kernel_name reports "interpn::k_lattice_fields_rows<T, method, N, rectilinear, fma,
+ *           fields_last>" after a fused evaluation.
+ * Checks    before any device work, in this order: fields NULL: INTERPN_HIP_ERR_INVALID_ARGUMENT; the checks of
+ *           interpn_hip_eval_lattice_device in their order with their statuses (an empty axis: INTERPN_HIP_OK, nothing
+ *           written); then a layout value other than the two, out_stride below prod(axis_lens) (field-major) or below K
+ *           (fields-last), or a result whose bytes do not fit size_t: INTERPN_HIP_ERR_INVALID_ARGUMENT.
+ * Failing   regular grids only.  The first failing lattice index in C order over axis_lens is the same for every field
+ * points    (the field axis is not part of it).  Device form: interpn_hip_fields_finish reports it, on both paths.  Host
+ *           form: the set's status, *first_bad_index = i, and exactly the results in front of it are written: out[f][0..i)
+ *           for every f (field-major), rows [0, i) (fields-last); everything else is left as it was.
+ * ---------------------------------------------------------------------------------------- */
+enum { INTERPN_HIP_FIELDS_LATTICE_FIELD_MAJOR = 0, INTERPN_HIP_FIELDS_LATTICE_FIELDS_LAST = 1 };
+enum { INTERPN_HIP_FIELDS_LATTICE_PATH_FUSED = 0, INTERPN_HIP_FIELDS_LATTICE_PATH_PER_FIELD = 1 };
+/* Asynchronous on `stream`.  `axes`: HOST array of `naxes` DEVICE pointers; `out`: device.  `flags`:
+ * INTERPN_HIP_EVAL_NO_ALLOC.  *path_taken (may be NULL): INTERPN_HIP_FIELDS_LATTICE_PATH_*. */
+int interpn_hip_fields_eval_lattice_device(interpn_hip_fields* fields, const void* const* axes, const size_t* axis_lens,
+                                           size_t naxes, void* out, size_t out_stride, int layout, void* stream, unsigned flags,
+                                           int* path_taken);
+/* The same on host arrays, synchronous: chunks of leading-axis indices of about 2^25 / K points each (option "host_chunk":
+ * points per chunk).  Shares the sticky status words with the device form: finish device evaluations first. */
+int interpn_hip_fields_eval_lattice_host(interpn_hip_fields* fields, const void* const* axes, const size_t* axis_lens,
+                                         size_t naxes, void* out, size_t out_stride, int layout, uint64_t* first_bad_index);
+/* Scratch blocks for lattices of up to these axis lengths on up to `nstreams` concurrent streams: every handle gets what
+ * interpn_hip_reserve_lattice gives it, the first handle twice the blocks, each also large enough for the per-field
+ * path's slice of K rows.  A handle holds 4 blocks at most, and a per-field evaluation with fields-last results holds two
+ * of the first handle's at a time: for THAT form the guarantee covers two concurrent streams, not more — a third stream's
+ * evaluation under INTERPN_HIP_EVAL_NO_ALLOC or graph capture can return INTERPN_HIP_ERR_OUT_OF_MEMORY.  The fused path
+ * and field-major results are covered up to 4 streams.  Synchronous. */
+int interpn_hip_fields_reserve_lattice(interpn_hip_fields* fields, const size_t* axis_lens, size_t naxes, int nstreams);
+/* Which path (INTERPN_HIP_FIELDS_LATTICE_PATH_*) a set of `nfields` fields takes on a lattice of `axis_lens` on a grid of
+ * `dims` with results in `layout`, G and the fused workgroup's LDS bytes (both 0 on the per-field path) and the
+ * overflow-checked point count.  Needs no device; arguments, statuses and latched environment as for
+ * interpn_hip_lattice_plan, checked first; then nfields == 0 or another layout value: INTERPN_HIP_ERR_INVALID_ARGUMENT. */
+int interpn_hip_fields_lattice_plan(size_t elem_size, int method, size_t ndims, const size_t* dims, const size_t* axis_lens,
+                                    size_t nfields, int layout, int* path, size_t* group, size_t* lds_bytes, size_t* npoints);
+
+/* ------------------------------------------------------------------------------------------
  * Point-major observation points — the points as ONE array of shape (npoints, N), the layout of particle positions, ray
  * samples and scipy's `xi`, instead of N coordinate arrays.
  *

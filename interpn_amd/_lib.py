@@ -35,6 +35,8 @@ FLAVOUR_FMA, FLAVOUR_NO_FMA = 0x100, 0x200  # OR-ed into `method` of interpn_hip
 PATH_IN_PLACE, PATH_BINNED, PATH_SWEEP = 0, 1, 2
 FIELDS_PATH_FUSED, FIELDS_PATH_PER_FIELD = 0, 1  # interpn_hip_fields_eval_device
 FIELDS_POINTS_PATHS = {0: "fused", 1: "split"}  # interpn_hip_fields_eval_points_device
+FIELDS_LATTICE_FIELD_MAJOR, FIELDS_LATTICE_FIELDS_LAST = 0, 1  # interpn_hip_fields_eval_lattice_device: `layout`
+FIELDS_LATTICE_PATHS = {0: "fused", 1: "per_field"}  # ... and its paths
 LATTICE_PATH_FUSED, LATTICE_PATH_EXPANDED = 0, 1  # interpn_hip_eval_lattice_device
 LATTICE_PATHS = {LATTICE_PATH_FUSED: "fused", LATTICE_PATH_EXPANDED: "expanded"}
 POINTS_PATHS = {0: "fused", 1: "split", 2: "direct"}  # interpn_hip_eval_points_device
@@ -186,6 +188,13 @@ def load() -> ctypes.CDLL:
                                                           ctypes.c_uint, POINTER(c_int)]
     lib.interpn_hip_fields_eval_points_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t]
     lib.interpn_hip_fields_reserve_points.argtypes = [c_void_p, c_size_t, c_int]
+    lib.interpn_hip_fields_eval_lattice_device.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_size_t,
+                                                           c_int, c_void_p, ctypes.c_uint, POINTER(c_int)]
+    lib.interpn_hip_fields_eval_lattice_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_size_t,
+                                                         c_int, POINTER(c_uint64)]
+    lib.interpn_hip_fields_reserve_lattice.argtypes = [c_void_p, POINTER(c_size_t), c_size_t, c_int]
+    lib.interpn_hip_fields_lattice_plan.argtypes = [c_size_t, c_int, c_size_t, POINTER(c_size_t), POINTER(c_size_t), c_size_t, c_int,
+                                                    POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]
     lib.interpn_hip_eval_lattice_device.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_void_p,
                                                     ctypes.c_uint, POINTER(c_int)]
     lib.interpn_hip_eval_lattice_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p,

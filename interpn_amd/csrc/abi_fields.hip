@@ -3,43 +3,13 @@
 // every tuned path the single handles have) and, for multilinear N = 2, 3, the fused kernel's table
 // (linear_fields.h).  Behind the column form, the point-major form of the same sets ("Point-major field sets": the fused
 // kernel of linear_fields_points.h on that table, or slices that are de-interleaved, evaluated by the column form and
-// joined).  (C ABI internals, see abi_internal.h.)
+// joined).  The lattice form of a set lives in abi_fields_lattice.hip.  (C ABI internals, see abi_internal.h.)
 #include <climits>
 
 #include "abi_internal.h"
 
 using namespace interpn;
 using namespace interpn_abi;
-
-struct interpn_hip_fields {
-  int device = 0;
-  int dtype = kF64;
-  int ndims = 0;
-  size_t nfields = 0;
-  size_t field_stride = 0;        // elements from field to field in `vals`
-  size_t field_elems = 0;         // elements of one field
-  int per_line = 0;               // fused table: fields per line (P) and lines per cell
-  size_t lines = 0;
-  void* vals_owned = nullptr;     // device copy of the whole buffer when created from host memory
-  const void* vals = nullptr;     // device, field-major
-  std::vector<interpn_hip_interp*> sub;  // one handle per field
-  void* table = nullptr;          // the fused kernel's table, or null: per-field only
-  size_t table_bytes = 0;
-  int fused = -1;                 // option: -1 automatic, 0 never, 1 wherever the table exists
-  int last_path = INTERPN_HIP_FIELDS_PATH_PER_FIELD;
-  int points_path = -1;           // option, point-major form: -1 automatic, 1 fused wherever the table exists, 2 split
-  int last_points_path = -1;      // INTERPN_HIP_FIELDS_POINTS_PATH_* of the last point-major call, -1 before any
-  bool sub_tables = true;         // the K handles have built their own re-laid tables (false: deferred)
-  bool per_field_pending = false; // per-field evaluations since the last finish: every handle's status word counts
-  std::mutex mu;                  // the deferred table build
-  std::mutex host_mu;             // host evaluations share the staging below: serialised
-  // host evaluation: one stream, the coordinates of a chunk and its K result rows on the device
-  hipStream_t stream = nullptr;
-  unsigned long long* kit_word = nullptr;
-  void* host_obs = nullptr;
-  void* host_out = nullptr;
-  size_t host_points = 0;
-};
 
 namespace {
 
@@ -56,6 +26,9 @@ long long env_number(const char* name, long long fallback) {
   return (end == env || *end != 0) ? fallback : v;
 }
 
+}  // namespace
+
+namespace interpn_abi {
 // The K handles' own tables, once (the per-field path's first use outside capture).
 int ensure_sub_tables(interpn_hip_fields* s) {
   std::lock_guard<std::mutex> lk(s->mu);
@@ -67,6 +40,9 @@ int ensure_sub_tables(interpn_hip_fields* s) {
   s->sub_tables = true;
   return INTERPN_HIP_OK;
 }
+}  // namespace interpn_abi
+
+namespace {
 
 // Which path an evaluation of `npoints` points on `stream` takes when the caller leaves it to the set (fused = -1).
 // Measured (profiles/fields_bench.json): the fused kernel runs at the Infinity Cache's rate for
@@ -222,8 +198,6 @@ int eval_columns(interpn_hip_fields* s, bool fused, const void* const* obs, void
 // ---- point-major form ---------------------------------------------------------------------------------------------------
 
 using Slot = interpn_hip_interp::BinSlot;
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Points per slice of the split path: the slice's N coordinate arrays and K result rows together stay within what
 // kExpandSliceBytes allows the coordinate arrays of a handle's slice; whole multiples of 256 points (slices then begin
@@ -611,6 +585,9 @@ int interpn_hip_fields_get_option(const interpn_hip_fields* s, const char* name,
   if (!strcmp(name, "last_path")) { *value = s->last_path; return INTERPN_HIP_OK; }
   if (!strcmp(name, "points_path")) { *value = s->points_path; return INTERPN_HIP_OK; }
   if (!strcmp(name, "last_points_path")) { *value = s->last_points_path; return INTERPN_HIP_OK; }
+  // (the set's own, not the first handle's: a per-field lattice evaluation leaves "fused" or "expanded" there)
+  if (!strcmp(name, "last_lattice_path")) { *value = s->last_lattice_path; return INTERPN_HIP_OK; }
+  if (!strcmp(name, "last_lattice_group")) { *value = s->last_lattice_group; return INTERPN_HIP_OK; }
   if (!strncmp(name, "evals_", 6)) {  // the per-field path evaluates through every handle: their counters, summed
     long long sum = 0;
     for (const interpn_hip_interp* h : s->sub) {

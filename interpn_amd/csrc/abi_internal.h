@@ -11,6 +11,8 @@
 //   abi_bounds.hip    check_bounds
 //   abi_sharded.hip   single-process multi-GPU forms
 //   abi_grad.hip      value and gradient of a multilinear or multicubic handle (eval_grad_* / eval_cubic_grad_*)
+//   abi_fields.hip    field sets: creation, column and point-major forms, options
+//   abi_fields_lattice.hip  field sets on a lattice (fields_eval_lattice_device / _host, fields_reserve_lattice, fields_lattice_plan)
 //   abi_points.hip    point-major observation points (eval_points_device / _host, reserve_points) and their gradient form
 //                     (eval_points_grad_device / _host, reserve_points_grad)
 #pragma once
@@ -209,6 +211,44 @@ struct interpn_hip_interp {
   } sampling;
 };
 
+// A field set (abi_fields.hip, abi_fields_lattice.hip).
+struct interpn_hip_fields {
+  int device = 0;
+  int dtype = interpn::kF64;
+  int ndims = 0;
+  size_t nfields = 0;
+  size_t field_stride = 0;        // elements from field to field in `vals`
+  size_t field_elems = 0;         // elements of one field
+  int per_line = 0;               // fused table: fields per line (P) and lines per cell
+  size_t lines = 0;
+  void* vals_owned = nullptr;     // device copy of the whole buffer when created from host memory
+  const void* vals = nullptr;     // device, field-major
+  std::vector<interpn_hip_interp*> sub;  // one handle per field
+  void* table = nullptr;          // the fused kernel's table, or null: per-field only
+  size_t table_bytes = 0;
+  int fused = -1;                 // option: -1 automatic, 0 never, 1 wherever the table exists
+  int last_path = INTERPN_HIP_FIELDS_PATH_PER_FIELD;
+  int points_path = -1;           // option, point-major form: -1 automatic, 1 fused wherever the table exists, 2 split
+  int last_points_path = -1;      // INTERPN_HIP_FIELDS_POINTS_PATH_* of the last point-major call, -1 before any
+  int last_lattice_path = -1;     // INTERPN_HIP_FIELDS_LATTICE_PATH_* of the last lattice call, -1 before any
+  int last_lattice_group = 0;     // G of the last fused lattice call
+  bool sub_tables = true;         // the K handles have built their own re-laid tables (false: deferred)
+  bool per_field_pending = false; // per-field evaluations since the last finish: every handle's status word counts
+  std::mutex mu;                  // the deferred table build
+  std::mutex host_mu;             // host evaluations share the staging below: serialised
+  // host evaluation: one stream, the coordinates of a chunk and its K result rows on the device
+  hipStream_t stream = nullptr;
+  unsigned long long* kit_word = nullptr;
+  void* host_obs = nullptr;
+  void* host_out = nullptr;
+  size_t host_points = 0;
+};
+
+namespace interpn {
+struct LatticeShape;
+struct LatticePlan;
+}  // namespace interpn
+
 namespace interpn_abi {
 
 // ---------------------------------------------------------------------------
@@ -310,6 +350,24 @@ template <typename T>
 int create_one_dim(int method, int kind, T start, T step, const T* grid, size_t ngrid, const T* vals, size_t nvals,
                    int vals_mem, int device, interpn_hip_interp** handle);
 
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Whether `stream` is being captured into a graph; a failed query counts as captured (nothing is allocated or waited for).
+inline bool stream_capturing(hipStream_t stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); return true; }
+  return cs != hipStreamCaptureStatusNone;
+}
+
+// The status of a sequence of launches through `h` that failed half-way: part of it may be in flight without a stream mark
+// behind it, so interpn_hip_destroy synchronises the device.
+inline int fail_sequence(interpn_hip_interp* h, hipError_t err, int st) {
+  (void)hipGetLastError();
+  std::lock_guard<std::mutex> lk(h->marks_mu);
+  h->sync_device_at_destroy = true;
+  return err != hipSuccess ? hip_fail(err) : st;
+}
+
 // abi_launch.hip
 hipError_t launch_any(const GridDesc& g, const void* const* obs, void* out, size_t npts,
                       unsigned long long* first_bad, hipStream_t stream);
@@ -334,8 +392,26 @@ interpn_hip_interp::BinSlot* take_slot_captured(interpn_hip_interp* h, size_t ne
 void release_slot_captured(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot);
 void claim_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot);
 int reserve_slots(interpn_hip_interp* h, size_t need, int nstreams);
+// ... and what the lattice forms of a field set (abi_fields_lattice.hip) share with the single handle's: the shape of a
+// lattice from the caller's arrays, the checks every lattice entry point makes (in this order; *empty: some axis has no
+// coordinates), the scratch one evaluation needs on the path `plan` names, the larger of the two paths' needs (reserve),
+// and one lattice on device arrays through the handle.
+// (`*indexable`: the grid's values are indexed with 32 bits; `n`: the grid's axis lengths as the plans take them) the
+// argument checks the two plan entry points share.
+int lattice_plan_args(size_t elem_size, int method, size_t ndims, const size_t* dims, const size_t* axis_lens, int* n,
+                      interpn::LatticeShape* s, bool* indexable);
+int lattice_make_shape(const void* const* axes, const size_t* axis_lens, size_t naxes, interpn::LatticeShape* s);
+int validate_lattice(const interpn_hip_interp* h, const void* const* axes, const size_t* axis_lens, size_t naxes, const void* out,
+                     interpn::LatticeShape* s, bool* empty);
+interpn::LatticePlan lattice_plan_for(const GridDesc& g, const interpn::LatticeShape& s);
+size_t lattice_scratch_need(const GridDesc& g, const interpn::LatticeShape& s, const interpn::LatticePlan& p);
+size_t lattice_reserve_need(const GridDesc& g, const interpn::LatticeShape& s);
+int lattice_device(interpn_hip_interp* h, const interpn::LatticeShape& s, void* out, hipStream_t stream, unsigned flags, int* path_taken);
 constexpr size_t kExpandSliceBytes = (size_t)64 << 20;  // coordinates of one slice (bounds the scratch block)
 constexpr size_t kExpandSliceMin = (size_t)1 << 16;     // ... but never fewer points than this
+
+// abi_fields.hip
+int ensure_sub_tables(interpn_hip_fields* s);
 
 // abi_grad.hip: the column form's gradient launch, k_linear_grad / k_cubic_grad or the runtime-N kernels by the handle's
 // method and each launcher's own rule (also the middle step of the point-major split path, abi_points.hip)

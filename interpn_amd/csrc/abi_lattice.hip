@@ -82,11 +82,13 @@ namespace {
 
 constexpr size_t kHostChunkPointsLattice = (size_t)1 << 25;  // host form: lattice points per chunk of leading-axis indices
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+}  // namespace
+
+namespace interpn_abi {
 
 // Shape of a lattice from the caller's arrays.  INVALID_ARGUMENT: the point count does not fit size_t;
 // UNSUPPORTED: more than 2^31 axis coordinates in all.
-int make_shape(const void* const* axes, const size_t* axis_lens, size_t naxes, LatticeShape* s) {
+int lattice_make_shape(const void* const* axes, const size_t* axis_lens, size_t naxes, LatticeShape* s) {
   s->ndims = (int)naxes;
   size_t np = 0;
   if (!checked_product(axis_lens, naxes, &np)) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
@@ -109,12 +111,12 @@ int make_shape(const void* const* axes, const size_t* axis_lens, size_t naxes, L
   return INTERPN_HIP_OK;
 }
 
-LatticePlan plan_for(const GridDesc& g, const LatticeShape& s) {
+LatticePlan lattice_plan_for(const GridDesc& g, const LatticeShape& s) {
   if (!fast_path(g) || g.cfg.force_generic) return LatticePlan();  // 64-bit grids and the testing route: the handle's own kernels
   return lattice_plan(g.method, g.ndims, g.dtype == kF64 ? 8 : 4, g.n, s.m, lattice_lds_budget(g.cfg), g.cfg.num_cus, g.cfg.lattice);
 }
 
-size_t expand_slice(const GridDesc& g, size_t npoints) {
+static size_t expand_slice(const GridDesc& g, size_t npoints) {
   const size_t elem = g.dtype == kF64 ? 8 : 4;
   size_t slice = kExpandSliceBytes / ((size_t)g.ndims * elem);
   if (slice < kExpandSliceMin) slice = kExpandSliceMin;
@@ -123,7 +125,7 @@ size_t expand_slice(const GridDesc& g, size_t npoints) {
 }
 
 // Bytes of the scratch block one evaluation needs.
-size_t scratch_need(const GridDesc& g, const LatticeShape& s, const LatticePlan& p) {
+size_t lattice_scratch_need(const GridDesc& g, const LatticeShape& s, const LatticePlan& p) {
   const size_t elem = g.dtype == kF64 ? 8 : 4;
   if (p.fused) return align_up(s.coords * lattice_record_bytes(g.method, g.kind, elem), 256);
   const size_t flags = g.kind == kRegular ? align_up(s.coords, 256) : 0;
@@ -133,12 +135,10 @@ size_t scratch_need(const GridDesc& g, const LatticeShape& s, const LatticePlan&
 // One lattice on device arrays.  Arguments are validated; the current device is the handle's.
 int lattice_device(interpn_hip_interp* h, const LatticeShape& s, void* out, hipStream_t stream, unsigned flags, int* path_taken) {
   const GridDesc& g = h->desc;
-  const LatticePlan plan = plan_for(g, s);
+  const LatticePlan plan = lattice_plan_for(g, s);
   const size_t elem = g.dtype == kF64 ? 8 : 4;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-  const bool capturing = cs != hipStreamCaptureStatusNone;
-  const size_t need = scratch_need(g, s, plan);
+  const bool capturing = stream_capturing(stream);
+  const size_t need = lattice_scratch_need(g, s, plan);
   Slot* slot = nullptr;
   if (need) {
     int why = INTERPN_HIP_WHY_NONE;
@@ -173,12 +173,7 @@ int lattice_device(interpn_hip_interp* h, const LatticeShape& s, void* out, hipS
     if (capturing) release_slot_captured(h, slot);
     else release_bin_slot(h, slot, stream, false);
   }
-  if (err != hipSuccess || st != INTERPN_HIP_OK) {
-    (void)hipGetLastError();
-    std::lock_guard<std::mutex> lk(h->marks_mu);
-    h->sync_device_at_destroy = true;  // part of the sequence may be in flight without a mark behind it
-    return err != hipSuccess ? hip_fail(err) : st;
-  }
+  if (err != hipSuccess || st != INTERPN_HIP_OK) return fail_sequence(h, err, st);
   const int path = plan.fused ? INTERPN_HIP_LATTICE_PATH_FUSED : INTERPN_HIP_LATTICE_PATH_EXPANDED;
   h->desc.last_lattice_path = path;
   if (path_taken) *path_taken = path;
@@ -193,7 +188,7 @@ int validate_lattice(const interpn_hip_interp* h, const void* const* axes, const
   if (is_one_dim(h->desc.method)) return INTERPN_HIP_ERR_UNSUPPORTED;
   int st = validate_obs(h->desc, nullptr, naxes, 0);
   if (st) return st;
-  st = make_shape(axes, axis_lens, naxes, s);
+  st = lattice_make_shape(axes, axis_lens, naxes, s);
   if (st) return st;
   *empty = s->npoints == 0;
   if (*empty) return INTERPN_HIP_OK;
@@ -203,28 +198,50 @@ int validate_lattice(const interpn_hip_interp* h, const void* const* axes, const
   return INTERPN_HIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int interpn_hip_lattice_plan(size_t elem_size, int method, size_t ndims, const size_t* dims, const size_t* axis_lens,
-                             int* path, size_t* lds_bytes, size_t* npoints) {
+// What interpn_hip_lattice_plan and interpn_hip_fields_lattice_plan check, in this order.
+int lattice_plan_args(size_t elem_size, int method, size_t ndims, const size_t* dims, const size_t* axis_lens, int* n, LatticeShape* s,
+                      bool* indexable) {
   method &= 0xFF;
   if ((elem_size != 4 && elem_size != 8) || (method != kLinear && method != kCubic && method != kNearest)) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
   if (ndims < 1 || ndims > 8 || !dims || !axis_lens) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
   const size_t minlen = method == kCubic ? 4 : 2;
   const size_t maxlen = elem_size == 8 ? max_axis_len<double>() : max_axis_len<float>();
-  int n[8] = {0};
   for (size_t d = 0; d < ndims; ++d) {
     if (dims[d] < minlen) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
     if (dims[d] > maxlen) return INTERPN_HIP_ERR_UNSUPPORTED;
     n[d] = (int)dims[d];
   }
-  LatticeShape s;
-  int st = make_shape(nullptr, axis_lens, ndims, &s);
+  int st = lattice_make_shape(nullptr, axis_lens, ndims, s);
   if (st) return st;
   size_t nvals = 0;
-  const bool indexable = checked_product(dims, ndims, &nvals) && nvals < 0xFFFFFFFFull;
+  *indexable = checked_product(dims, ndims, &nvals) && nvals < 0xFFFFFFFFull;
+  return INTERPN_HIP_OK;
+}
+
+// Whichever path the options in force at evaluation time choose: the larger of the two blocks.
+size_t lattice_reserve_need(const GridDesc& g, const LatticeShape& s) {
+  LatticePlan fused = lattice_plan_for(g, s), expanded;
+  size_t need = lattice_scratch_need(g, s, expanded);
+  if (fused.covered && fused.fits) {
+    fused.fused = true;
+    const size_t nf = lattice_scratch_need(g, s, fused);
+    if (nf > need) need = nf;
+  }
+  return need;
+}
+
+}  // namespace interpn_abi
+
+extern "C" {
+
+int interpn_hip_lattice_plan(size_t elem_size, int method, size_t ndims, const size_t* dims, const size_t* axis_lens,
+                             int* path, size_t* lds_bytes, size_t* npoints) {
+  int n[8] = {0};
+  LatticeShape s;
+  bool indexable = false;
+  const int st = lattice_plan_args(elem_size, method, ndims, dims, axis_lens, n, &s, &indexable);
+  if (st) return st;
+  method &= 0xFF;
   LaunchConfig c;  // the defaults of a handle on an MI355X, with the environment a new handle would latch
   latch_env(c);
   LatticePlan p;
@@ -255,19 +272,12 @@ int interpn_hip_reserve_lattice(interpn_hip_interp* h, const size_t* axis_lens, 
   int st = validate_obs(h->desc, nullptr, naxes, 0);
   if (st) return st;
   LatticeShape s;
-  st = make_shape(nullptr, axis_lens, naxes, &s);
+  st = lattice_make_shape(nullptr, axis_lens, naxes, &s);
   if (st) return st;
   if ((size_t)nstreams > interpn_hip_interp::kMaxBinSlots) nstreams = (int)interpn_hip_interp::kMaxBinSlots;
   if (s.npoints == 0 || nstreams == 0) return INTERPN_HIP_OK;
   const GridDesc& g = h->desc;
-  // whichever path the options in force at evaluation time choose: the larger of the two blocks
-  LatticePlan fused = plan_for(g, s), expanded;
-  size_t need = scratch_need(g, s, expanded);
-  if (fused.covered && fused.fits) {
-    fused.fused = true;
-    const size_t nf = scratch_need(g, s, fused);
-    if (nf > need) need = nf;
-  }
+  const size_t need = lattice_reserve_need(g, s);
   DeviceGuard guard(h->device);
   if (!guard.ok()) return INTERPN_HIP_ERR_NO_DEVICE;
   return reserve_slots(h, need, nstreams);
@@ -309,7 +319,7 @@ int interpn_hip_eval_lattice_host(interpn_hip_interp* h, const void* const* axes
       sub_lens[d] = d == 0 ? cnt0 : s.m[d];
     }
     LatticeShape sub;
-    st = make_shape(sub_axes, sub_lens, (size_t)s.ndims, &sub);
+    st = lattice_make_shape(sub_axes, sub_lens, (size_t)s.ndims, &sub);
     if (st) break;
     st = lattice_device(h, sub, dev_out, l.stream, 0u, nullptr);
     if (st) break;

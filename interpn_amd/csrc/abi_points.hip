@@ -13,8 +13,6 @@ constexpr size_t kPointsChunk = (size_t)2 << 20;
 
 using Slot = interpn_hip_interp::BinSlot;
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // Points per slice of the split path: the coordinates of a slice are bounded like those of the lattice's expanded path.
 size_t split_slice(const GridDesc& g, size_t npoints) {
   const size_t elem = g.dtype == kF64 ? 8 : 4;

@@ -89,6 +89,59 @@ inline size_t lattice_lds_budget(const LaunchConfig& c) {
   return c.axis_lds_kb >= 0 ? (size_t)c.axis_lds_kb * 1024 : thresholds(c).axis_lds;
 }
 
+// ---- Field sets on a lattice (k_lattice_fields.hip) ----------------------------------------------------------------------
+// K fields of one grid on one lattice: the records of a lattice do not depend on the field, so one axes launch serves all
+// of them, and k_lattice_fields_rows puts a field loop around k_lattice_rows' row.  Fields are processed in groups of G: a
+// wave owns G lines (line f = dims 0..N-2 of field f0 + f reduced at every grid column); a lane then loads the last axis's
+// record ONCE per output and evaluates one node per field of the group.  Two result layouts:
+//   field-major   out[f * out_stride + p]: each field's row segment stored coalesced, as k_lattice_rows does.
+//   fields-last   out[p * out_stride + f]: the wave stages a [64][G] tile in LDS (rows (G | 1) elements apart: an odd
+//                 pitch keeps the lanes of a column off one bank) and stores its 64 G elements lane-contiguously.
+// LDS of a workgroup and the group size:
+//   wave_bytes(g) = g * lattice_line_bytes(n_{N-1}, elem) + (fields-last ? round16(64 * (g | 1) * elem) : 0)
+//   G             = the largest g in 1 .. min(K, kLatticeFieldsCap) with kLatticeWaves * wave_bytes(g) <= budget, 0 if none
+//   lds_bytes     = kLatticeWaves * wave_bytes(G)
+// kLatticeFieldsCap = 8: what a larger group still saves is the last axis's record load, 1 / G of it per output and field,
+// and at G = 8 a point's run of a fields-last row is already a whole 32-byte sector in f32 and a whole 64-byte request in
+// f64, while the tile (4.5 KiB per wave in f64) has taken most of a wave's default 5 KiB share.  From the cost model, not
+// from a measurement: no measured row has K > 4.
+constexpr int kLatticeFieldsCap = 8;
+enum LatticeFieldsLayout : int { kLatticeFieldMajor = 0, kLatticeFieldsLast = 1 };
+
+inline size_t lattice_fields_tile_bytes(size_t g, size_t elem) { return ((size_t)64 * (g | 1) * elem + 15) & ~(size_t)15; }
+inline size_t lattice_fields_wave_bytes(size_t n_last, size_t elem, size_t g, int layout) {
+  return g * lattice_line_bytes(n_last, elem) + (layout == kLatticeFieldsLast ? lattice_fields_tile_bytes(g, elem) : 0);
+}
+
+// Which path a field set takes on a lattice.  Fused when lattice_plan says fused for the mode and a group of at least one
+// field fits (field-major: exactly lattice_plan's `fits`; fields-last: the tile of one field on top).  Automatic mode adds
+// nothing for a set.  A first form of the rule sent fields-last results with short runs per point (G != K and G * elem <
+// 16: partial-sector stores) through the per-field path; measured, the fused kernel wins the rows that condition would
+// have turned away (G = 1 of K = 3, 4) by 1.16 .. 1.38 against K single evaluations and a stack — what the per-field path
+// amounts to there, plus a join — and by 1.69 .. 2.76 against the per-field path with expansion
+// (profiles/fields_lattice_bench.json: ratio_baseline_over_fused, ratio_per_field_over_fused), so
+// that condition is gone.
+struct FieldsLatticePlan {
+  bool fused = false;
+  size_t group = 0;       // G on the fused path (0 otherwise)
+  size_t lds_bytes = 0;   // of a workgroup on the fused path (0 otherwise)
+};
+inline FieldsLatticePlan fields_lattice_plan(int method, int ndims, size_t elem, const int* n, const size_t* m, size_t nfields,
+                                             int layout, size_t budget, int num_cus, int mode) {
+  FieldsLatticePlan p;
+  const LatticePlan one = lattice_plan(method, ndims, elem, n, m, budget, num_cus, mode);
+  if (!one.fused || nfields == 0) return p;
+  const size_t n_last = (size_t)n[ndims - 1];
+  const size_t top = nfields < (size_t)kLatticeFieldsCap ? nfields : (size_t)kLatticeFieldsCap;
+  size_t g = 0;
+  while (g < top && (size_t)kLatticeWaves * lattice_fields_wave_bytes(n_last, elem, g + 1, layout) <= budget) ++g;
+  if (g == 0) return p;
+  p.fused = true;
+  p.group = g;
+  p.lds_bytes = (size_t)kLatticeWaves * lattice_fields_wave_bytes(n_last, elem, g, layout);
+  return p;
+}
+
 // The lattice as the kernels see it (host arrays of at most kMaxDims entries).
 struct LatticeShape {
   int ndims = 0;
@@ -113,5 +166,10 @@ hipError_t launch_lattice_rows(const GridDesc& g, const LatticeShape& s, const v
 // slice-relative failing index (the axes kernel has reported the lattice's).
 hipError_t launch_lattice_expand(const GridDesc& g, const LatticeShape& s, const unsigned char* bad, void* const* dst,
                                  size_t begin, size_t count, hipStream_t stream);
+// k_lattice_fields.hip
+// The rows of `nfields` fields (field f at g.vals + f * field_stride elements) from the records of launch_lattice_axes:
+// groups of `group` fields, `lds_bytes` as fields_lattice_plan gives them; `layout`, `out_stride` as above.
+hipError_t launch_lattice_fields_rows(const GridDesc& g, const LatticeShape& s, const void* recs, size_t field_stride, size_t nfields,
+                                      size_t group, void* out, size_t out_stride, int layout, size_t lds_bytes, hipStream_t stream);
 
 }  // namespace interpn

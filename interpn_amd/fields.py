@@ -18,6 +18,43 @@ from . import _lib
 from .raw import _check_arr, _dims, _slice_of_slices
 
 
+def _field_axis(field_axis) -> int:
+    if field_axis not in (0, -1):
+        raise ValueError("field_axis: expected 0 (fields first) or -1 (fields last)")
+    return _lib.FIELDS_LATTICE_FIELD_MAJOR if field_axis == 0 else _lib.FIELDS_LATTICE_FIELDS_LAST
+
+
+def _lattice_out_stride(shape, strides, k, m, layout, contiguous) -> int:
+    """The element stride a lattice result of `shape` / `strides` (in elements) hands to the library, for K fields on a
+    lattice of axis lengths `m`; ValueError for a wrong shape or a layout the kernels cannot write."""
+    count = int(np.prod(m, dtype=object)) if m else 0
+    shape, m = tuple(int(v) for v in shape), tuple(m)
+    if layout == _lib.FIELDS_LATTICE_FIELD_MAJOR:
+        if shape != (k,) + m and shape != (k, count):
+            raise ValueError(f"out: expected shape {(k,) + m}, got {shape}")
+        if count == 0:
+            return 0
+        inner, want = strides[1:], 1  # each field's block in C order
+        for n, st in zip(reversed(shape[1:]), reversed(inner)):
+            if n > 1 and st != want:
+                raise ValueError("out: each field's block must be contiguous")
+            want *= n
+        if k > 1 and strides[0] < count:
+            raise ValueError(f"out: the stride from field to field must be at least {count} elements")
+        return int(strides[0]) if k > 1 else count
+    if shape == m + (k,) and contiguous:
+        return k
+    if len(shape) == 2 and shape == (count, k):
+        if count and k > 1 and strides[1] != 1:
+            raise ValueError("out: every row must be contiguous (unit stride along the last axis)")
+        if count > 1 and strides[0] < k:
+            raise ValueError(f"out: the row stride must be at least {k} elements")
+        return int(strides[0]) if count > 1 else k
+    if shape != m + (k,):
+        raise ValueError(f"out: expected shape {m + (k,)}, got {shape}")
+    raise ValueError(f"out: expected a C-contiguous array, or a 2-D ({count}, >= {k}) view with contiguous rows")
+
+
 def _is_tensor(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
 
@@ -326,6 +363,105 @@ class Fields:
             raise TypeError(f"eval_points on a host array takes no {sorted(kwargs)}")
         return self.eval_points_host(pts, out)
 
+    # -- lattice evaluation: one coordinate vector per axis in, (K, *m) or (*m, K) values out ----
+    @property
+    def last_lattice_path(self):
+        """"fused" (one launch of `interpn::k_lattice_fields_rows` for all fields) or "per_field" (K lattice evaluations
+        through the K interpolators): what the most recent lattice evaluation did (None before any)."""
+        return _lib.FIELDS_LATTICE_PATHS.get(self.get_option("last_lattice_path"))
+
+    def reserve_lattice(self, axis_lens, nstreams: int = 1) -> None:
+        """Pre-allocate the scratch of lattice evaluations with up to these axis lengths on up to `nstreams` concurrent
+        streams (`interpn_hip_fields_reserve_lattice`); afterwards they work with `no_alloc=True` and under graph
+        capture.  Per-field evaluations with `field_axis=-1` hold two blocks of the first field's interpolator at a time,
+        of the four it can have: for them the guarantee covers two concurrent streams."""
+        lens, n = _dims(axis_lens)
+        _lib.raise_for_status(_lib.load().interpn_hip_fields_reserve_lattice(self._h, lens, n, int(nstreams)))
+
+    def eval_lattice_host(self, axes, out=None, field_axis: int = 0) -> np.ndarray:
+        """Every field on the lattice axes[0] x .. x axes[N-1] of host coordinate vectors (synchronous;
+        `interpn_hip_fields_eval_lattice_host`): an array of shape `(K, *m)`, or `(*m, K)` with `field_axis=-1`, m =
+        the vectors' lengths, whose field f has the bits of `Interpolator.eval_lattice_host` of that field alone.
+        `out`, field-major: every field's block contiguous, any stride from field to field; fields-last: a C-contiguous
+        array, or a 2-D `(prod(m), >= K)` view with contiguous rows.  On "Unrepresentable coordinate value" the
+        AssertionError carries `first_bad_index` (C order over m) and exactly the results in front of it are written,
+        for every field."""
+        layout = _field_axis(field_axis)
+        aptr, alen, naxes, _keep = _slice_of_slices("axes", axes, self.dtype)
+        m = tuple(int(alen[i]) for i in range(naxes))
+        k, item = self.nfields, self.dtype.itemsize
+        if out is None:
+            out = np.zeros((k,) + m if field_axis == 0 else m + (k,), dtype=self.dtype)
+        if not isinstance(out, np.ndarray):
+            raise TypeError(f"argument 'out': expected a numpy array, got {type(out).__name__}")
+        if out.dtype != self.dtype:
+            raise TypeError(f"argument 'out': expected dtype {self.dtype.name}, got {out.dtype.name}")
+        if any(st % item for st in out.strides):
+            raise ValueError("out: strides must be whole numbers of elements")
+        stride = _lattice_out_stride(out.shape, [st // item for st in out.strides], k, m, layout, out.flags.c_contiguous)
+        if not out.flags.writeable:
+            raise ValueError("argument 'out': array is read-only")
+        vp = (c_void_p * max(naxes, 1))()
+        for i in range(naxes):
+            vp[i] = ctypes.cast(aptr[i], c_void_p)
+        bad = c_uint64(0)
+        st = _lib.load().interpn_hip_fields_eval_lattice_host(self._h, vp, alen, naxes, c_void_p(out.ctypes.data), stride, layout,
+                                                             ctypes.byref(bad))
+        if st in _lib.UNREPRESENTABLE:
+            err = AssertionError(_lib.strerror(st))
+            err.first_bad_index = bad.value
+            raise err
+        _lib.raise_for_status(st)
+        return out
+
+    def eval_lattice_tensors(self, axes, out=None, field_axis: int = 0, stream=None, no_alloc: bool = False):
+        """The same on torch CUDA tensors (asynchronous on torch's current stream unless given;
+        `interpn_hip_fields_eval_lattice_device`): `axes` are contiguous 1-D tensors of the set's dtype.  `out` must not
+        overlap them.  `last_lattice_path` says which path ran; `finish()` synchronises and raises for a coordinate the
+        reference cannot evaluate, with `first_bad_index` in C order over m (the same for every field)."""
+        import torch
+
+        layout = _field_axis(field_axis)
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        axes = list(axes)
+        dev = self.device() if self._h is not None and self._h.value else -1
+        for i, t in enumerate(axes):
+            if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
+                raise TypeError(f"axes[{i}]: expected a contiguous 1-D {want} CUDA tensor")
+            if t.device.index not in (None, dev):
+                raise ValueError(f"axes[{i}] is on {t.device} but this set lives on cuda:{dev}")
+        m = tuple(int(t.numel()) for t in axes)
+        k = self.nfields
+        if out is None:
+            out = torch.empty((k,) + m if field_axis == 0 else m + (k,), dtype=want, device=torch.device("cuda", dev))
+        if not (hasattr(out, "is_cuda") and out.is_cuda and out.dtype == want):
+            raise TypeError(f"out: expected a {want} CUDA tensor")
+        if out.device.index not in (None, dev):
+            raise ValueError(f"out is on {out.device} but this set lives on cuda:{dev}")
+        stride = _lattice_out_stride(out.shape, out.stride(), k, m, layout, out.is_contiguous())
+        owner = torch.cuda.current_stream(dev) if stream is None else stream
+        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        n = len(axes)
+        vp = (c_void_p * max(n, 1))(*[t.data_ptr() for t in axes])
+        lens = (ctypes.c_size_t * max(n, 1))(*m)
+        path = ctypes.c_int(0)
+        st = _lib.load().interpn_hip_fields_eval_lattice_device(self._h, vp, lens, n, c_void_p(out.data_ptr()), stride, layout,
+                                                               c_void_p(int(raw)), _lib.EVAL_NO_ALLOC if no_alloc else 0,
+                                                               ctypes.byref(path))
+        _lib.raise_for_status(st)
+        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        return out
+
+    def eval_lattice(self, axes, out=None, **kwargs):
+        """`eval_lattice_tensors` for torch tensors, `eval_lattice_host` for numpy arrays (by the type of `axes[0]`)."""
+        axes = list(axes)
+        if axes and _is_tensor(axes[0]):
+            return self.eval_lattice_tensors(axes, out, **kwargs)
+        extra = sorted(set(kwargs) - {"field_axis"})
+        if extra:
+            raise TypeError(f"eval_lattice on host arrays takes no {extra}")
+        return self.eval_lattice_host(axes, out, **kwargs)
+
     def finish(self, stream=None) -> None:
         """Wait for the evaluations enqueued since the last finish; AssertionError("Unrepresentable coordinate
         value") with `.first_bad_index` if a point could not be evaluated (the same index for every field)."""
@@ -370,6 +506,86 @@ def fields_layout(dtype, dims, nfields: int):
     _lib.raise_for_status(_lib.load().interpn_hip_fields_layout(np.dtype(dtype).itemsize, nd, d, int(nfields), ctypes.byref(per_line),
                                                                 ctypes.byref(lines), ctypes.byref(nbytes)))
     return int(per_line.value), int(lines.value), int(nbytes.value)
+
+
+def fields_lattice_plan(dtype, method: str, dims, axis_lens, nfields: int, field_axis: int = 0):
+    """(path, group, lds_bytes, npoints): the path ("fused" / "per_field") a set of `nfields` fields takes in automatic mode
+    on a lattice of `axis_lens` coordinates per axis of a grid of `dims`, the fields per pass G and the LDS bytes of the
+    fused kernel's workgroup (both 0 on the per-field path), and the point count (`interpn_hip_fields_lattice_plan`; needs
+    no device)."""
+    layout = _field_axis(field_axis)
+    d, nd = _dims(dims)
+    m, nm = _dims(axis_lens)
+    if nd != nm:
+        raise ValueError(f"axis_lens: expected {nd} lengths, got {nm}")
+    path, group, lds, npts = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    st = _lib.load().interpn_hip_fields_lattice_plan(np.dtype(dtype).itemsize, _lib.METHODS[method], nd, d, m, int(nfields), layout,
+                                                     ctypes.byref(path), ctypes.byref(group), ctypes.byref(lds), ctypes.byref(npts))
+    _lib.raise_for_status(st)
+    return _lib.FIELDS_LATTICE_PATHS[path.value], int(group.value), int(lds.value), int(npts.value)
+
+
+def interpn_fields_lattice(axes, grids, vals, *, method="linear", field_axis: int = 0, out=None,
+                           linearize_extrapolation: bool = True, assume_regular: bool = False):
+    """`interpn_lattice()` for K fields on one grid: every field on the lattice axes[0] x .. x axes[N-1] in one pass.  The
+    rules are those of `interpn_lattice` and `interpn_fields` (inputs ravelled, dtype from `vals`, exact-spacing regularity
+    test, host arrays or torch CUDA tensors as coordinate vectors).
+
+    `vals` has shape (K, *dims) and the result (K, *m), m = the vectors' lengths; with `field_axis=-1` the channel-last
+    layout: `vals` (*dims, K), result (*m, K) — an image resize when N = 2."""
+    from . import _check_regular, _is_cuda_tensor
+
+    _field_axis(field_axis)
+    if method not in ("linear", "cubic", "nearest"):
+        raise ValueError(f"Unsupported interpolation configuration: {method}")
+    if not (isinstance(vals, np.ndarray) or _is_tensor(vals)):
+        raise TypeError("vals: expected a numpy array or a torch tensor with a field axis")
+    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
+    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
+    if len(vals.shape) < 2:
+        raise ValueError("vals: expected a field axis besides the grid's values")
+    axes = list(axes)
+    grids = [np.ascontiguousarray(np.asarray(g).ravel()).astype(dtype, copy=False) for g in grids]
+    if len(axes) != len(grids):
+        raise ValueError(f"axes: expected {len(grids)} coordinate vectors (one per grid axis), got {len(axes)}")
+    nper = int(np.prod([g.size for g in grids], dtype=object))
+    k = int(vals.shape[field_axis])
+    if k * nper != int(np.prod(tuple(vals.shape), dtype=object)):
+        raise ValueError(f"vals: expected {k} x {nper} values for grids of {[g.size for g in grids]}, got shape {tuple(vals.shape)}")
+    if field_axis == -1:  # (*dims, K) -> (K, prod(dims)), once: set-up, not part of the pass over the lattice
+        vals = vals.reshape(nper, k).T
+    vals = (vals.contiguous() if _is_tensor(vals) else np.ascontiguousarray(vals)).reshape(k, nper)
+    on_device = bool(axes) and _is_cuda_tensor(axes[0])
+    m = tuple(int(a.numel()) if _is_tensor(a) else int(np.asarray(a).size) for a in axes)
+    rshape = (k,) + m if field_axis == 0 else m + (k,)
+    if out is not None and tuple(out.shape) != rshape:
+        raise ValueError(f"out: expected shape {rshape}, got {tuple(out.shape)}")
+    device = -1
+    if on_device:
+        import torch
+
+        device = axes[0].device.index if axes[0].device.index is not None else torch.cuda.current_device()
+        axes = [a.reshape(-1).contiguous() for a in axes]
+    else:
+        if _is_tensor(vals):
+            vals = vals.cpu().numpy()
+        axes = [np.ascontiguousarray(np.asarray(a).ravel()) for a in axes]
+    if assume_regular or _check_regular(grids):
+        starts = np.array([g[0] for g in grids], dtype=dtype)
+        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
+        fs = Fields.regular(method, [g.size for g in grids], starts, steps, vals, linearize_extrapolation=linearize_extrapolation,
+                            device=device, dtype=dtype)
+    else:
+        fs = Fields.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
+    try:
+        if on_device:
+            res = fs.eval_lattice_tensors(axes, out, field_axis=field_axis)
+            fs.finish()
+        else:
+            res = fs.eval_lattice_host(axes, out, field_axis=field_axis)
+    finally:
+        fs.close()
+    return res
 
 
 def interpn_fields(obs, grids, vals, *, method="linear", field_axis: int = 0, out=None, linearize_extrapolation: bool = True,
