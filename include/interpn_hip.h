@@ -78,6 +78,13 @@
  *                                       measured, 1 = no clock); INTERPN_HIP_SWEEP_LAYOUT=11|12 (creation only, 3-D f64
  *                                       multilinear: the sweep kernel's table with one line per cell / 1.5 lines per cell at half
  *                                       the size; default: by the table's size against the points an XCD holds per sweep)
+ *       INTERPN_HIP_FINISH_KERNEL=1|0   interpn_hip_finish / interpn_hip_fields_finish: how the 8-byte status word reaches the host.
+ *                                       1 (default): a one-lane kernel behind the evaluations on the stream stores it into pinned
+ *                                       memory (a field set's K words travel as their minimum: one command, one wait).  0: an
+ *                                       8-byte hipMemcpyAsync per handle; a stream under capture always takes the copy.  Either
+ *                                       way finish then calls hipStreamSynchronize: when it returns, everything enqueued on
+ *                                       `stream` before the call is complete for the device and for the HIP runtime — results may
+ *                                       be consumed on any stream, and an event recorded before the call reads complete
  *       INTERPN_HIP_BIN_SLICE_LOG2=n    log2 of the points sorted per slice (16..27, default 25): bounds a scratch block
  *       INTERPN_HIP_AXIS_RECORDS=0      rectilinear multilinear: search with coordinates + tables, not per-bucket records
  *       INTERPN_HIP_CUBIC_RECORDS=n     rectilinear multicubic (creation only): per-cell records of the axes (cubic_cell_record.h: a

@@ -47,19 +47,38 @@ int binned_applies(const GridDesc& g, size_t npoints) {
   return 2;
 }
 
+bool settle_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot& sl) {
+  if (!sl.unmarked) return true;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  hipError_t e = hipStreamIsCapturing(sl.last_stream, &cs);
+  if (e == hipSuccess && cs != hipStreamCaptureStatusNone) return false;
+  if (e == hipSuccess) e = hipEventRecord(sl.event, sl.last_stream);
+  sl.unmarked = false;
+  sl.recorded = e == hipSuccess;
+  if (e != hipSuccess) {
+    // no event behind the work (the caller has destroyed that stream, say): make it complete before anyone reuses the block
+    (void)hipGetLastError();
+    if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
+    std::lock_guard<std::mutex> lk(h->marks_mu);
+    h->sync_device_at_destroy = true;
+  }
+  return true;
+}
+
 // Take a scratch block of at least `need` bytes for an evaluation on `stream` (see BinSlot).
 // On success the block is marked busy and, where another stream used it last, `stream` has been
-// made to wait for that use.  `*why` says why not otherwise.
+// made to wait for that use (whose event is recorded at this moment, not when the use ended).
+// `*why` says why not otherwise.
 interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, hipStream_t stream, bool may_alloc, int* why) {
   using Slot = interpn_hip_interp::BinSlot;
   std::unique_lock<std::mutex> lk(h->bin_mu);  // (step 5 drops it around a wait)
   Slot* pick = nullptr;
   bool wait = false;
   for (auto& sl : h->bin_slots)  // 1. the block this stream used last: stream order is enough
-    if (!sl.busy && sl.bytes >= need && sl.recorded && sl.last_stream == stream) { pick = &sl; break; }
+    if (!sl.busy && sl.bytes >= need && (sl.recorded || sl.unmarked) && sl.last_stream == stream) { pick = &sl; break; }
   if (!pick)
     for (auto& sl : h->bin_slots) {  // 2. an idle block
-      if (sl.busy || sl.bytes < need) continue;
+      if (sl.busy || sl.bytes < need || !settle_slot(h, sl)) continue;
       if (!sl.recorded) { pick = &sl; break; }
       const hipError_t q = hipEventQuery(sl.event);
       if (q == hipSuccess) { pick = &sl; break; }
@@ -79,14 +98,15 @@ interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, h
     h->bin_slots.push_back(sl);
     pick = &h->bin_slots.back();
   }
+  // (from here on every candidate has been through settle_slot in step 2: `unmarked` means its stream is being captured)
   if (!pick) {  // 4. the least recently used block that is large enough: wait for it on the device
     for (auto& sl : h->bin_slots)
-      if (!sl.busy && sl.bytes >= need && (!pick || sl.stamp < pick->stamp)) pick = &sl;
+      if (!sl.busy && !sl.unmarked && sl.bytes >= need && (!pick || sl.stamp < pick->stamp)) pick = &sl;
     wait = pick != nullptr;
   }
   if (!pick && may_alloc) {  // 5. grow the least recently used block that nobody is enqueueing into
     for (auto& sl : h->bin_slots)
-      if (!sl.busy && (!pick || sl.stamp < pick->stamp)) pick = &sl;
+      if (!sl.busy && settle_slot(h, sl) && (!pick || sl.stamp < pick->stamp)) pick = &sl;
     if (pick) {
       // The block's last use must complete before it is freed.  That wait and the reallocation
       // run WITHOUT the lock (the slot is marked busy, so nobody else takes it): other threads
@@ -133,18 +153,13 @@ interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, h
   return pick;
 }
 
-// Ends an evaluation's use of a block from take_bin_slot: whatever was enqueued — also a sequence cut short by a failure — is
-// followed by the block's event, so that the next user of the block on another stream waits for it.  `staged`: the block's
-// stage events were recorded by this use (option stage_timing).
+// Ends an evaluation's use of a block from take_bin_slot.  Nothing goes onto the stream: the block remembers the stream, and
+// whoever needs an event behind this use — also behind a sequence cut short by a failure — records it then (settle_slot).
+// `staged`: the block's stage events were recorded by this use (option stage_timing).
 void release_bin_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot, hipStream_t stream, bool staged) {
   std::lock_guard<std::mutex> lk(h->bin_mu);
-  if (hipEventRecord(slot->event, stream) == hipSuccess) {
-    slot->recorded = true;
-  } else {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(stream);  // no event behind the work: make it complete before anyone reuses the block
-    slot->recorded = false;
-  }
+  slot->unmarked = true;
+  slot->recorded = false;
   slot->last_stream = stream;
   slot->busy = false;
   slot->staged = staged;
@@ -406,7 +421,7 @@ int interpn_hip_reserve(interpn_hip_interp* h, size_t npoints, int nstreams) {
   // grow blocks that are too small first (idle ones only), then add new ones
   for (auto& sl : h->bin_slots) {
     if (have >= nstreams) break;
-    if (sl.bytes >= need || sl.busy) continue;
+    if (sl.bytes >= need || sl.busy || !settle_slot(h, sl)) continue;
     if (sl.recorded) HIP_TRY(hipEventSynchronize(sl.event));
     pool_free(h->device, sl.scratch);
     h->sampling.last_word = nullptr;

@@ -572,15 +572,19 @@ void interpn_hip_destroy(interpn_hip_interp* h) {
   if (!h) return;
   DeviceGuard guard(h->device);
   // Blocks go back to the pool only once nothing in flight can still touch them.  Wait for the
-  // work THIS handle enqueued — the event behind the last launch on every caller stream it was
-  // given, and its own lane streams — not for the whole device: unrelated streams (a training
-  // step on the same GPU) keep running.  Launches that could not be marked fall back to
-  // hipDeviceSynchronize.
+  // caller streams THIS handle enqueued on, and its own lane streams — not for the whole device:
+  // unrelated streams (a training step on the same GPU) keep running.  Launches put no marker on
+  // their stream (mark_stream), so the wait covers what a stream holds now.  Launches that could
+  // not be marked, a stream the caller has destroyed since and one that is being captured (never
+  // touched) fall back to hipDeviceSynchronize.
   {
     std::lock_guard<std::mutex> lk(h->marks_mu);
-    for (auto& m : h->marks) {
-      if (hipEventSynchronize(m.event) != hipSuccess) { (void)hipGetLastError(); h->sync_device_at_destroy = true; }
-      (void)hipEventDestroy(m.event);
+    for (hipStream_t m : h->marks) {
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(m, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone || hipStreamSynchronize(m) != hipSuccess) {
+        (void)hipGetLastError();
+        h->sync_device_at_destroy = true;
+      }
     }
     h->marks.clear();
   }

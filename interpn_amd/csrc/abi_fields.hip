@@ -387,6 +387,13 @@ int interpn_hip_fields_finish(interpn_hip_fields* s, void* stream, uint64_t* fir
   // in each: the cell search does not depend on the field)
   const size_t count = s->per_field_pending ? s->nfields : 1;
   s->per_field_pending = false;
+  if (count > 1 && count <= (size_t)kMaxStatusWords) {
+    // the K words behind ONE command and one wait: the status kernel delivers their minimum (abi_host.hip)
+    unsigned long long* words[kMaxStatusWords];
+    for (size_t f = 0; f < count; ++f) words[f] = s->sub[f]->first_bad;
+    const int st = finish_words(s->sub[0], static_cast<hipStream_t>(stream), words, (int)count, first_bad_index);
+    if (st >= 0) return st;
+  }
   int error = INTERPN_HIP_OK;
   uint64_t best = ~(uint64_t)0;
   for (size_t f = 0; f < count; ++f) {

@@ -149,10 +149,10 @@ static int eval_host_small(interpn_hip_interp* h, const void* const* obs, void* 
   void* dev_out = (char*)h->small_dev + (size_t)8 * stride;
   HIP_TRY(launch_any(h->desc, dev_obs, dev_out, nout, l.flag_dev, l.stream));
   HIP_TRY(hipMemcpyAsync(l.flag_host, l.flag_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, l.stream));
-  // The runtime's wait, not wait_status_word: here the RESULTS are written by the kernel straight
-  // into pinned host memory, and the status word landing (a copy-engine write) does not order
-  // those shader writes for the CPU — watching the word alone returned stale results once in
-  // 37 739 fuzz cases.
+  // The runtime's wait, not a spin on the status word: here the RESULTS are written by the kernel
+  // straight into pinned host memory, and the status word landing (a copy-engine write) does not
+  // order those shader writes for the CPU — watching the word alone returned stale results once
+  // in 37 739 fuzz cases.
   HIP_TRY(hipStreamSynchronize(l.stream));
   const unsigned long long bad = *l.flag_host;
   size_t good = nout;
@@ -218,22 +218,29 @@ int eval_host_impl(interpn_hip_interp* h, const void* const* obs, size_t nobs, v
 
 namespace {
 // The status word to the host by a one-lane kernel instead of a copy-engine transfer (round 6): ordered behind the evaluation
-// like any kernel on the stream, it stores the 8 bytes into the pinned word with ONE system-scope store (never torn), and
-// costs a dispatch (~4 us) where the 8-byte hipMemcpyAsync costs ~10.  What the host may conclude from seeing the word is
-// what it concluded from the copy: everything enqueued on the stream before it is complete on the device.
-__global__ void k_status_to_host(const unsigned long long* dev_word, unsigned long long* host_word) {
-  const unsigned long long v = __hip_atomic_load(dev_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// like any kernel on the stream, it stores the 8 bytes into the pinned word with ONE system-scope store (never torn).  With
+// the runtime's wait behind either, the kernel is 0.6 us cheaper than the 8-byte hipMemcpyAsync for one word, and the words
+// of several handles (a field set's) travel as their minimum — every one is an index of the same points or ~0 — behind one
+// command instead of K copies (profiles/step_commands.md).
+struct StatusWords {
+  const unsigned long long* word[interpn_abi::kMaxStatusWords];
+  int count;
+};
+__global__ void k_status_to_host(StatusWords w, unsigned long long* host_word) {
+  unsigned long long v = ~0ull;
+  for (int k = 0; k < w.count; ++k) {
+    const unsigned long long x = __hip_atomic_load(w.word[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    v = x < v ? x : v;
+  }
   __hip_atomic_store(host_word, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 }  // namespace
 
-extern "C" {
+namespace interpn_abi {
 
-int interpn_hip_finish(interpn_hip_interp* h, void* stream, uint64_t* first_bad_index) {
-  if (!h) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+int finish_words(interpn_hip_interp* h, hipStream_t s, unsigned long long* const* words, int count, uint64_t* first_bad_index) {
   DeviceGuard guard(h->device);
   if (!guard.ok()) return INTERPN_HIP_ERR_NO_DEVICE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   // The status word lands in pinned memory: a plain DMA behind the kernel, no staging copy.
   std::lock_guard<std::mutex> lk(h->finish_mu);
   if (!h->finish_word) {
@@ -242,29 +249,40 @@ int interpn_hip_finish(interpn_hip_interp* h, void* stream, uint64_t* first_bad_
     if (hipHostGetDevicePointer(&dp, h->finish_word, 0) == hipSuccess) h->finish_word_dev = static_cast<unsigned long long*>(dp);
     else (void)hipGetLastError();
   }
-  *(volatile unsigned long long*)h->finish_word = kWordPending;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const bool by_kernel = h->finish_word_dev && h->desc.cfg.finish_kernel != 0 &&
-                         hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
+  const hipError_t asked = hipStreamIsCapturing(s, &cs);
+  if (asked != hipSuccess) (void)hipGetLastError();  // the query's own failure, nothing an earlier call left pending
+  const bool by_kernel = h->finish_word_dev && h->desc.cfg.finish_kernel != 0 && count <= kMaxStatusWords && asked == hipSuccess &&
+                         cs == hipStreamCaptureStatusNone;
+  if (!by_kernel && count > 1) return -1;
   if (by_kernel) {
-    hipLaunchKernelGGL(k_status_to_host, dim3(1), dim3(1), 0, s, (const unsigned long long*)h->first_bad, h->finish_word_dev);
+    StatusWords w;
+    for (int k = 0; k < kMaxStatusWords; ++k) w.word[k] = words[k < count ? k : 0];
+    w.count = count;
+    hipLaunchKernelGGL(k_status_to_host, dim3(1), dim3(1), 0, s, w, h->finish_word_dev);
     HIP_TRY(hipGetLastError());
   } else {
-    (void)hipGetLastError();
-    HIP_TRY(hipMemcpyAsync(h->finish_word, h->first_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h->finish_word, words[0], sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   }
-  HIP_TRY(wait_status_word(s, h->finish_word));
+  // The runtime's wait, not a spin on the landing word: the word can reach the host microseconds before the runtime has
+  // retired the commands in front of it, and an event recorded before this call then still reads "not ready" (64 - 116 of
+  // 2 000 calls when the copy's landing was watched instead; 4 us per small call is what the difference costs).
+  HIP_TRY(hipStreamSynchronize(s));
   const unsigned long long word = *(volatile unsigned long long*)h->finish_word;
   if (word == kNoBadIndexHost) return INTERPN_HIP_OK;
-  HIP_TRY(hipMemsetAsync(h->first_bad, 0xFF, sizeof(word), s));
+  for (int k = 0; k < count; ++k) HIP_TRY(hipMemsetAsync(words[k], 0xFF, sizeof(word), s));
   HIP_TRY(hipStreamSynchronize(s));
-  // Read the index only now: the spin above may have seen the word while the copy engine was
-  // half-way through it (anything that is neither "pending" nor "clean" ends the spin); behind
-  // the synchronisation the 8 bytes are complete.
-  const unsigned long long settled = *(volatile unsigned long long*)h->finish_word;
-  if (settled == kNoBadIndexHost) return INTERPN_HIP_OK;  // cannot happen for a monotone MIN word; harmless
-  if (first_bad_index) *first_bad_index = (uint64_t)settled;
+  if (first_bad_index) *first_bad_index = (uint64_t)word;
   return h->desc.unrep_status;
+}
+
+}  // namespace interpn_abi
+
+extern "C" {
+
+int interpn_hip_finish(interpn_hip_interp* h, void* stream, uint64_t* first_bad_index) {
+  if (!h) return INTERPN_HIP_ERR_INVALID_ARGUMENT;
+  return finish_words(h, static_cast<hipStream_t>(stream), &h->first_bad, 1, first_bad_index);
 }
 
 int interpn_hip_eval_host(interpn_hip_interp* h, const void* const* obs, const size_t* obs_lens, size_t nobs,

@@ -5,7 +5,7 @@
 //   abi_layout.hip    which re-laid copy of the grid a handle keeps (bricks, tiles, 1-D records)
 //   abi_options.hip   per-handle options, kernel name, table size
 //   abi_create.hip    create / replicate / destroy, status strings
-//   abi_launch.hip    kernel dispatch of one evaluation, stream marks, status-word wait
+//   abi_launch.hip    kernel dispatch of one evaluation, stream marks
 //   abi_binned.hip    sorted (binned / column) evaluation of device-resident batches
 //   abi_host.hip      host-pointer pipeline, small-batch path, finish, one-shot entry points
 //   abi_bounds.hip    check_bounds
@@ -141,14 +141,15 @@ struct interpn_hip_interp {
   unsigned long long* finish_word_dev = nullptr;  // ... as the device sees it (the status kernel's target), or null
   std::mutex finish_mu;
   std::mutex host_mu;  // host-pointer evaluations on one handle share its two lanes: serialised
-  // Caller streams that device-pointer work was enqueued on, each with an event recorded behind
-  // the most recent such launch: interpn_hip_destroy waits for exactly these (and its own lane
-  // streams) instead of stalling the whole device.  `sync_device_at_destroy` is set for launches
-  // that could not be marked (a stream under capture, more than kMaxMarks streams, event failure).
+  // Caller streams that device-pointer work was enqueued on: interpn_hip_destroy waits for exactly
+  // these (and its own lane streams) instead of stalling the whole device.  Remembering a stream
+  // puts nothing on it: a launch costs no command beyond its kernels, and destroy waits for
+  // whatever the stream holds by then.  `sync_device_at_destroy` is set for launches that could
+  // not be marked (a stream under capture, more than kMaxMarks streams) and for streams that
+  // cannot be waited for any more (destroyed by the caller).
   static constexpr size_t kMaxMarks = 16;
-  struct StreamMark { hipStream_t stream; hipEvent_t event; };
   std::mutex marks_mu;
-  std::vector<StreamMark> marks;
+  std::vector<hipStream_t> marks;
   bool sync_device_at_destroy = false;
   // Host-evaluation workspace (lazily allocated, reused across calls): two pipeline lanes so
   // that the upload of one chunk overlaps the download of the previous one.
@@ -165,12 +166,15 @@ struct interpn_hip_interp {
   void* small_host = nullptr;
   void* small_dev = nullptr;
   // Binned evaluation (interpn_host.h): scratch for one slice of sorted points, shared by every
-  // evaluation through this handle.  `bin_event` is recorded behind the last use; the next user
-  // makes its stream wait for it, so two streams never work in the scratch at the same time.
+  // evaluation through this handle.  Two streams never work in a block at the same time: a block
+  // remembers the stream that used it last, and its event is recorded behind that use only when
+  // somebody else needs to know (settle_slot) — another stream that takes the block and waits
+  // for the event, or a block about to be freed.
   // Up to kMaxBinSlots blocks, one per stream that evaluates concurrently: an evaluation takes
-  // the block its stream used last (stream order alone makes the reuse safe), else an idle one,
-  // else makes a new one (unless told not to allocate), else waits — on the device, through the
-  // block's event — for the least recently used one.  `bin_mu` guards the slot list and the
+  // the block its stream used last (stream order alone makes the reuse safe: no event, no
+  // command on the stream), else an idle one, else makes a new one (unless told not to
+  // allocate), else waits — on the device, through the block's event — for the least recently
+  // used one.  `bin_mu` guards the slot list and the
   // per-handle report fields (desc.last_binned, desc.tag of a binned launch); the launches
   // themselves are enqueued outside it.
   static constexpr size_t kMaxBinSlots = 4;
@@ -178,7 +182,8 @@ struct interpn_hip_interp {
     void* scratch = nullptr;
     size_t bytes = 0;
     hipEvent_t event = nullptr;
-    bool recorded = false;       // `event` has been recorded at least once
+    bool recorded = false;       // `event` has been recorded behind the block's last use
+    bool unmarked = false;       // the last use may be in flight on `last_stream` with no event behind it yet (settle_slot)
     bool busy = false;           // a host thread is enqueueing into this block right now
     hipStream_t last_stream = nullptr;
     unsigned long long stamp = 0;  // use counter value of the last use (LRU)
@@ -376,13 +381,24 @@ void mark_stream(interpn_hip_interp* h, hipStream_t stream);
 // (8 dims x 8 B x 4 Mi = 256 MiB worst case) while each kernel launch still fills the chip.
 constexpr size_t kHostChunkPoints = (size_t)4 << 20;
 
-constexpr unsigned long long kWordPending = 0xFFFFFFFFFFFFFFFEull;  // neither "no failure" (~0) nor an index
-hipError_t wait_status_word(hipStream_t s, const unsigned long long* word);
+// abi_host.hip: what interpn_hip_finish does, for the first-failing-index words of `count` handles whose work is on `s`
+// (`h` lends its pinned word): ONE command behind that work brings the smallest of the words to the host, the stream is
+// synchronised, and — only when a point failed — every word is reset.  Returns a status, or -1 when the words cannot travel
+// together (more than kMaxStatusWords of them, a stream under capture, no device view of the pinned word, option
+// finish_kernel = 0) and count > 1: the caller then asks handle by handle.  One word travels by the status kernel too, or
+// by an 8-byte copy where the kernel cannot be used.
+constexpr int kMaxStatusWords = 32;
+int finish_words(interpn_hip_interp* h, hipStream_t s, unsigned long long* const* words, int count, uint64_t* first_bad_index);
 
 // abi_binned.hip
 int binned_applies(const GridDesc& g, size_t npoints);
 interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, hipStream_t stream, bool may_alloc, int* why);
 void release_bin_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot, hipStream_t stream, bool staged);
+// (bin_mu held) Makes the block's last use known to the runtime: records the block's event on the stream of that use, which
+// covers everything that stream holds by now.  Afterwards `recorded` says whether there is an event to wait for (none: the
+// block was never used, or its stream is gone and the device has been waited for instead).  False: that stream is being
+// captured and must not be touched — the block cannot be handed to anybody else right now.
+bool settle_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot& slot);
 
 // abi_lattice.hip: scratch blocks of the paths that fill one themselves and hand it to interpn_hip_eval_device_ex (the
 // lattice's expanded path, the point-major split path).  Under graph capture a block is taken without touching any event;

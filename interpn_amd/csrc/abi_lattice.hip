@@ -50,7 +50,7 @@ int reserve_slots(interpn_hip_interp* h, size_t need, int nstreams) {
     if (sl.bytes >= need) ++have;
   for (auto& sl : h->bin_slots) {  // grow idle blocks that are too small first, then add new ones (as interpn_hip_reserve)
     if (have >= nstreams) break;
-    if (sl.bytes >= need || sl.busy) continue;
+    if (sl.bytes >= need || sl.busy || !settle_slot(h, sl)) continue;
     if (sl.recorded) HIP_TRY(hipEventSynchronize(sl.event));
     pool_free(h->device, sl.scratch);
     h->sampling.last_word = nullptr;

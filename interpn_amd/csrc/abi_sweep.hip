@@ -38,12 +38,13 @@ struct SampleChoice {
   unsigned seq = 0;               // ... numbered so
 };
 
-// Decides the sample of this launch (handle's sampling state, under bin_mu) and remembers where its verdict will be.
+// Decides the sample of this launch (handle's sampling state, under bin_mu); where a sample's verdict will be is noted once the
+// launch has its scratch block.
 // Thinned-out sampling (option sweep_probe = 2): a handle whose last three samples all said "unordered" is sampled on every
 // 16th automatic launch only (the sample and the gated launch behind the sweep kernel cost ~1.5 % of a 1e8-point launch),
 // and one whose last three said "coherent" runs the one-pass kernel alone in between; one verdict the other way brings every
 // launch's sample back.  Whichever kernel runs, the results are the same bits.
-SampleChoice choose_sample(interpn_hip_interp* h, const interpn_hip_interp::BinSlot* slot, size_t npoints) {
+SampleChoice choose_sample(interpn_hip_interp* h, size_t npoints) {
   const GridDesc& g = h->desc;
   SampleChoice c;
   c.sample = sweep_probe_applies(g) && npoints >= 256u * 64u;
@@ -80,7 +81,7 @@ SampleChoice choose_sample(interpn_hip_interp* h, const interpn_hip_interp::BinS
       }
     }
   }
-  s.last_word = c.sample ? static_cast<const unsigned char*>(slot->scratch) + sweep_probe_word_offset() : nullptr;
+  s.last_word = nullptr;
   return c;
 }
 
@@ -92,7 +93,8 @@ SampleChoice choose_sample(interpn_hip_interp* h, const interpn_hip_interp::BinS
 // taken per stream exactly like the sorted path's blocks (take_bin_slot): two streams never share
 // one in flight.  Not taken while the stream is being captured into a graph (the block's event
 // cannot be recorded there), for batches that give a wave fewer than four rounds, or for streams
-// that are not 16-byte aligned.
+// that are not 16-byte aligned.  A launch that runs the one-pass kernel alone (a handle in a streak of coherent batches)
+// needs no work words: it takes no block and puts nothing but its kernel on the stream.
 int eval_device_sweep(interpn_hip_interp* h, const void* const* obs, void* out, size_t npoints, hipStream_t stream,
                       unsigned flags, int* why) {
   const GridDesc& g = h->desc;
@@ -105,25 +107,33 @@ int eval_device_sweep(interpn_hip_interp* h, const void* const* obs, void* out, 
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); *why = INTERPN_HIP_WHY_CAPTURE; return -1; }
   if (cs != hipStreamCaptureStatusNone) { *why = INTERPN_HIP_WHY_CAPTURE; return -1; }
+  // automatic mode: the device decides between the sweep kernel and the one-pass kernel (k_linear_sweep.hip::k_sweep_probe:
+  // a sampling kernel in front, verdict 1 / 0 in the scratch block); both launches work from private copies of the
+  // description that carry the gate (the handle's own is shared by threads)
+  const SampleChoice c = choose_sample(h, npoints);
+  if (c.one_pass_only) {
+    GridDesc gb = g;
+    gb.launch_fat = true;  // (the workgroup shape of the gated launch: what coherent batches run best in)
+    const hipError_t e1 = launch_any(gb, obs, out, npoints, h->first_bad, stream);
+    g.tag = gb.tag;
+    if (e1 != hipSuccess) {
+      (void)hipGetLastError();
+      return hip_fail(e1);
+    }
+    return INTERPN_HIP_OK;
+  }
   interpn_hip_interp::BinSlot* slot = take_bin_slot(h, sweep_work_bytes(), stream, !(flags & INTERPN_HIP_EVAL_NO_ALLOC), why);
   if (!slot) return -1;
+  if (c.sample) {
+    std::lock_guard<std::mutex> lk(h->bin_mu);
+    h->sampling.last_word = static_cast<const unsigned char*>(slot->scratch) + sweep_probe_word_offset();
+  }
   hipError_t err = hipSuccess;
   // first use of the block by this path, or the sorted path has used it since: reset the work words (a complete launch leaves
   // its counters zero and its measured period in place; that period word is one of the sort's bin counters)
   if (!slot->sweep_clean) err = hipMemsetAsync(slot->scratch, 0, sweep_work_bytes(), stream);
-  // automatic mode: the device decides between the sweep kernel and the one-pass kernel (k_linear_sweep.hip::k_sweep_probe:
-  // a sampling kernel in front, verdict 1 / 0 in the scratch block); both launches work from private copies of the
-  // description that carry the gate (the handle's own is shared by threads)
-  const SampleChoice c = choose_sample(h, slot, npoints);
   if (c.sample && err == hipSuccess) err = launch_sweep_probe(g, obs, npoints, slot->scratch, stream, c.host_word, c.seq);
-  if (c.one_pass_only) {
-    if (err == hipSuccess) {
-      GridDesc gb = g;
-      gb.launch_fat = true;  // (the workgroup shape of the gated launch: what coherent batches run best in)
-      err = launch_any(gb, obs, out, npoints, h->first_bad, stream);
-      g.tag = gb.tag;
-    }
-  } else if (err == hipSuccess) {
+  if (err == hipSuccess) {
     if (c.sample) {
       GridDesc gs = g;
       gs.sweep_gated = true;

@@ -56,7 +56,7 @@ struct LaunchConfig {
   long long debug_stamps_bytes = 0;  // ... and the size of that buffer: a launch whose parts need more than it holds writes no stamps
   int bin_slice_log2 = 25; // binned evaluation: log2 of the points sorted and evaluated per slice (bounds a scratch block)
   int sweep = -1;          // 3-D f64 multilinear, device-pointer evaluation: the sweep kernel (linear_sweep.h) -1 where it pays, 0 never, 1 whenever the handle has its table
-  int finish_kernel = 0;   // interpn_hip_finish: 1 = the status word reaches the host by a one-lane kernel instead of an 8-byte copy (3.5 us less per call: 21.4 -> 17.8 us for a 1e3-point device call).  Off by default: the host then sees the word a few microseconds before the HIP runtime has retired the commands in front of it, and hipEventElapsedTime on an event recorded before finish() can still say "not ready" (observed once in ~1e4 calls); callers that only consume results or synchronise their events themselves can switch it on
+  int finish_kernel = 1;   // how interpn_hip_finish brings the status word to the host in front of its hipStreamSynchronize: 1 = a one-lane kernel (a field set's K words as their minimum behind one such kernel), 0 = an 8-byte copy per handle.  Measured (profiles/step_commands.md): a 1e3-point device call + finish 21.1 us by the kernel, 21.7 by the copy; a K = 8 per-field evaluation + finish 43 against 127 us
   int gated_iters = 4;     // rows of 256 lanes per workgroup of the gated brick launch behind an automatic sweep launch (an empty workgroup costs dispatch time)
   int sweep_probe = 2;     // automatic sweep launches: sample the batch on the device first and let the one-pass kernel take coherent batches — 0: never (the sweep kernel whatever the points look like), 1: every launch, 2: every launch until three samples in a row came out unordered, then every 16th (abi_sweep.hip)
   // (sweep itself: -1 automatic, 0 never, 1 always, 2 always with the sample deciding between the two kernels)
