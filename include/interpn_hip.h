@@ -472,7 +472,11 @@ size_t interpn_hip_table_bytes(const interpn_hip_interp* h, int* step_i, int* st
 /* Waits only for work enqueued through THIS handle (an event behind its last launch on every
  * caller stream, plus its own staging streams) before its device memory is recycled; other
  * streams of the device keep running.  Launches captured into a graph cannot be tracked: the
- * caller must not replay such a graph after destroying the handle. */
+ * caller must not replay such a graph after destroying the handle.
+ * The handle knows a caller stream by its hipStream_t value (scratch blocks are reused without any
+ * command by the stream that used them last, and streams are noted for this wait): synchronise a
+ * stream before destroying it while the handle lives, so that a new stream that is given the same
+ * value cannot meet work of the old one still in flight. */
 void interpn_hip_destroy(interpn_hip_interp* h);
 
 /* ------------------------------------------------------------------------------------------

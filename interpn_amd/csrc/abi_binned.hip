@@ -47,122 +47,15 @@ int binned_applies(const GridDesc& g, size_t npoints) {
   return 2;
 }
 
-bool settle_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot& sl) {
-  if (!sl.unmarked) return true;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  hipError_t e = hipStreamIsCapturing(sl.last_stream, &cs);
-  if (e == hipSuccess && cs != hipStreamCaptureStatusNone) return false;
-  if (e == hipSuccess) e = hipEventRecord(sl.event, sl.last_stream);
-  sl.unmarked = false;
-  sl.recorded = e == hipSuccess;
-  if (e != hipSuccess) {
-    // no event behind the work (the caller has destroyed that stream, say): make it complete before anyone reuses the block
-    (void)hipGetLastError();
-    if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-    std::lock_guard<std::mutex> lk(h->marks_mu);
-    h->sync_device_at_destroy = true;
-  }
-  return true;
-}
+// The scratch blocks' rules are scratch_slots.h's (settle, the five steps of take, release); these are its instances on HIP.
+bool settle_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot& sl) { return scratch_slots::settle_slot(*h, sl); }
 
-// Take a scratch block of at least `need` bytes for an evaluation on `stream` (see BinSlot).
-// On success the block is marked busy and, where another stream used it last, `stream` has been
-// made to wait for that use (whose event is recorded at this moment, not when the use ended).
-// `*why` says why not otherwise.
 interpn_hip_interp::BinSlot* take_bin_slot(interpn_hip_interp* h, size_t need, hipStream_t stream, bool may_alloc, int* why) {
-  using Slot = interpn_hip_interp::BinSlot;
-  std::unique_lock<std::mutex> lk(h->bin_mu);  // (step 5 drops it around a wait)
-  Slot* pick = nullptr;
-  bool wait = false;
-  for (auto& sl : h->bin_slots)  // 1. the block this stream used last: stream order is enough
-    if (!sl.busy && sl.bytes >= need && (sl.recorded || sl.unmarked) && sl.last_stream == stream) { pick = &sl; break; }
-  if (!pick)
-    for (auto& sl : h->bin_slots) {  // 2. an idle block
-      if (sl.busy || sl.bytes < need || !settle_slot(h, sl)) continue;
-      if (!sl.recorded) { pick = &sl; break; }
-      const hipError_t q = hipEventQuery(sl.event);
-      if (q == hipSuccess) { pick = &sl; break; }
-      if (q != hipErrorNotReady) (void)hipGetLastError();
-    }
-  if (!pick && may_alloc && h->bin_slots.size() < interpn_hip_interp::kMaxBinSlots) {  // 3. a new block
-    Slot sl;
-    if (hipEventCreateWithFlags(&sl.event, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); *why = INTERPN_HIP_WHY_ALLOC_FAILED; return nullptr; }
-    if (pool_alloc(h->device, &sl.scratch, need) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipEventDestroy(sl.event);
-      *why = INTERPN_HIP_WHY_ALLOC_FAILED;
-      return nullptr;
-    }
-    sl.bytes = need;
-    h->scratch_allocs.fetch_add(1);
-    h->bin_slots.push_back(sl);
-    pick = &h->bin_slots.back();
-  }
-  // (from here on every candidate has been through settle_slot in step 2: `unmarked` means its stream is being captured)
-  if (!pick) {  // 4. the least recently used block that is large enough: wait for it on the device
-    for (auto& sl : h->bin_slots)
-      if (!sl.busy && !sl.unmarked && sl.bytes >= need && (!pick || sl.stamp < pick->stamp)) pick = &sl;
-    wait = pick != nullptr;
-  }
-  if (!pick && may_alloc) {  // 5. grow the least recently used block that nobody is enqueueing into
-    for (auto& sl : h->bin_slots)
-      if (!sl.busy && settle_slot(h, sl) && (!pick || sl.stamp < pick->stamp)) pick = &sl;
-    if (pick) {
-      // The block's last use must complete before it is freed.  That wait and the reallocation
-      // run WITHOUT the lock (the slot is marked busy, so nobody else takes it): other threads
-      // keep enqueueing through this handle meanwhile.  Growth is synchronous for the caller —
-      // interpn_hip_reserve avoids it.
-      pick->busy = true;
-      const bool recorded = pick->recorded;
-      const hipEvent_t ev = pick->event;
-      void* const old = pick->scratch;
-      lk.unlock();
-      bool freed = false;
-      void* fresh = nullptr;
-      bool ok = !recorded || hipEventSynchronize(ev) == hipSuccess;
-      if (ok) {
-        pool_free(h->device, old);
-        freed = true;
-        ok = pool_alloc(h->device, &fresh, need) == hipSuccess;
-      }
-      if (!ok) (void)hipGetLastError();
-      lk.lock();
-      if (freed) h->sampling.last_word = nullptr;
-      pick->busy = false;
-      if (!ok) {
-        if (freed) { pick->scratch = nullptr; pick->bytes = 0; pick->recorded = false; }  // else the old block stays as it was
-        pick->totals_clean = false;
-        pick->sweep_clean = false;
-        *why = INTERPN_HIP_WHY_ALLOC_FAILED;
-        return nullptr;
-      }
-      pick->scratch = fresh;
-      pick->bytes = need;
-      pick->totals_clean = false;
-      pick->sweep_clean = false;
-      pick->recorded = false;
-      h->scratch_allocs.fetch_add(1);
-    }
-  }
-  if (!pick) { *why = INTERPN_HIP_WHY_NO_SCRATCH; return nullptr; }
-  if (wait && pick->recorded && pick->last_stream != stream &&
-      hipStreamWaitEvent(stream, pick->event, 0) != hipSuccess) { (void)hipGetLastError(); *why = INTERPN_HIP_WHY_NO_SCRATCH; return nullptr; }
-  if (!wait && pick->recorded && pick->last_stream != stream) (void)hipStreamWaitEvent(stream, pick->event, 0);  // complete already: free
-  pick->busy = true;
-  pick->stamp = ++h->bin_uses;
-  return pick;
+  return scratch_slots::take_bin_slot(*h, need, stream, may_alloc, why);
 }
 
-// Ends an evaluation's use of a block from take_bin_slot.  Nothing goes onto the stream: the block remembers the stream, and
-// whoever needs an event behind this use — also behind a sequence cut short by a failure — records it then (settle_slot).
-// `staged`: the block's stage events were recorded by this use (option stage_timing).
 void release_bin_slot(interpn_hip_interp* h, interpn_hip_interp::BinSlot* slot, hipStream_t stream, bool staged) {
-  std::lock_guard<std::mutex> lk(h->bin_mu);
-  slot->unmarked = true;
-  slot->recorded = false;
-  slot->last_stream = stream;
-  slot->busy = false;
-  slot->staged = staged;
+  scratch_slots::release_bin_slot(*h, slot, stream, staged);
 }
 
 // Binned evaluation of the tiled multicubic kernels on device-resident points (interpn_host.h).
@@ -414,39 +307,7 @@ int interpn_hip_reserve(interpn_hip_interp* h, size_t npoints, int nstreams) {
   const size_t slice_max = bin_slice_points(g);
   // the sorted path's slice, or the sweep kernel's work words (linear_sweep.h: 1.25 KiB per stream)
   const size_t need = sorts ? bin_scratch_bytes(g, npoints < slice_max ? npoints : slice_max) : sweep_work_bytes();
-  std::lock_guard<std::mutex> lk(h->bin_mu);
-  int have = 0;
-  for (auto& sl : h->bin_slots)
-    if (sl.bytes >= need) ++have;
-  // grow blocks that are too small first (idle ones only), then add new ones
-  for (auto& sl : h->bin_slots) {
-    if (have >= nstreams) break;
-    if (sl.bytes >= need || sl.busy || !settle_slot(h, sl)) continue;
-    if (sl.recorded) HIP_TRY(hipEventSynchronize(sl.event));
-    pool_free(h->device, sl.scratch);
-    h->sampling.last_word = nullptr;
-    sl.scratch = nullptr;
-    sl.bytes = 0;
-    sl.totals_clean = false;
-    sl.sweep_clean = false;
-    sl.recorded = false;
-    hipError_t e = pool_alloc(h->device, &sl.scratch, need);
-    if (e != hipSuccess) { (void)hipGetLastError(); sl.scratch = nullptr; return INTERPN_HIP_ERR_OUT_OF_MEMORY; }
-    sl.bytes = need;
-    h->scratch_allocs.fetch_add(1);
-    ++have;
-  }
-  while (have < nstreams && h->bin_slots.size() < interpn_hip_interp::kMaxBinSlots) {
-    interpn_hip_interp::BinSlot sl;
-    HIP_TRY(hipEventCreateWithFlags(&sl.event, hipEventDisableTiming));
-    hipError_t e = pool_alloc(h->device, &sl.scratch, need);
-    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(sl.event); return INTERPN_HIP_ERR_OUT_OF_MEMORY; }
-    sl.bytes = need;
-    h->scratch_allocs.fetch_add(1);
-    h->bin_slots.push_back(sl);
-    ++have;
-  }
-  return have >= nstreams ? INTERPN_HIP_OK : INTERPN_HIP_ERR_OUT_OF_MEMORY;
+  return reserve_slots(h, need, nstreams);
 }
 
 }  // extern "C"

@@ -576,21 +576,13 @@ void interpn_hip_destroy(interpn_hip_interp* h) {
   // unrelated streams (a training step on the same GPU) keep running.  Launches put no marker on
   // their stream (mark_stream), so the wait covers what a stream holds now.  Launches that could
   // not be marked, a stream the caller has destroyed since and one that is being captured (never
-  // touched) fall back to hipDeviceSynchronize.
-  {
-    std::lock_guard<std::mutex> lk(h->marks_mu);
-    for (hipStream_t m : h->marks) {
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(m, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone || hipStreamSynchronize(m) != hipSuccess) {
-        (void)hipGetLastError();
-        h->sync_device_at_destroy = true;
-      }
-    }
-    h->marks.clear();
-  }
-  for (auto& l : h->lane)
-    if (l.stream && hipStreamSynchronize(l.stream) != hipSuccess) { (void)hipGetLastError(); h->sync_device_at_destroy = true; }
-  if (h->sync_device_at_destroy) (void)hipDeviceSynchronize();
+  // touched) fall back to hipDeviceSynchronize.  (scratch_slots.h: destroy_wait)
+  scratch_slots::destroy_wait(*h, [h] {
+    bool ok = true;
+    for (auto& l : h->lane)
+      if (l.stream && hipStreamSynchronize(l.stream) != hipSuccess) { (void)hipGetLastError(); ok = false; }
+    return ok;
+  });
   for (auto& l : h->lane) {
     if (l.stream) pool_return_kit(h->device, l.stream, l.flag_host);
     pool_free(h->device, l.flag_dev);
@@ -598,12 +590,10 @@ void interpn_hip_destroy(interpn_hip_interp* h) {
     pool_free(h->device, l.out);
   }
   pool_return_small(h->device, h->small_host);
-  for (auto& sl : h->bin_slots) {  // their streams were waited for above (marks)
-    if (sl.event) (void)hipEventDestroy(sl.event);
+  scratch_slots::free_blocks(*h, [](interpn_hip_interp::BinSlot& sl) {  // their streams were waited for above (marks)
     for (hipEvent_t e : sl.stage)
       if (e) (void)hipEventDestroy(e);
-    pool_free(h->device, sl.scratch);
-  }
+  });
   pool_free(h->device, h->first_bad);
   pool_return_pinned_word(h->device, h->finish_word);
   pool_return_pinned_word(h->device, h->sampling.host);

@@ -13,6 +13,8 @@
 //   abi_grad.hip      value and gradient of a multilinear or multicubic handle (eval_grad_* / eval_cubic_grad_*)
 //   abi_fields.hip    field sets: creation, column and point-major forms, options
 //   abi_fields_lattice.hip  field sets on a lattice (fields_eval_lattice_device / _host, fields_reserve_lattice, fields_lattice_plan)
+//   scratch_slots.h   (no HIP in it) scratch blocks between streams and stream marks: settle / take / release / reserve /
+//                     mark / the wait at destroy, against a runtime type; HipRuntime below is the product's
 //   abi_points.hip    point-major observation points (eval_points_device / _host, reserve_points) and their gradient form
 //                     (eval_points_grad_device / _host, reserve_points_grad)
 #pragma once
@@ -36,6 +38,7 @@
 
 #include "../../include/interpn_hip.h"
 #include "interpn_host.h"
+#include "scratch_slots.h"
 
 namespace interpn {
 // Multilinear value and gradient in one pass (k_linear_grad.hip, linear_grad.h): `grad` is a host array of ndims device
@@ -126,9 +129,34 @@ struct DeviceProps { int num_cus = 256, num_xcds = 8; long long l2_bytes = 4 << 
 DeviceProps device_props(int device);
 int device_num_cus(int device);
 
+// The runtime scratch_slots.h runs on in the product: every member forwards to one hip* call or to the pool.
+struct HipRuntime {
+  using Stream = hipStream_t;
+  using Event = hipEvent_t;
+  static constexpr int kNotReady = (int)hipErrorNotReady;
+  const int* device = nullptr;  // the handle's (the current device whenever a block is allocated)
+  int is_capturing(Stream s, bool* capturing) const {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(s, &cs);
+    *capturing = cs != hipStreamCaptureStatusNone;
+    return (int)e;
+  }
+  int event_create(Event* ev) const { return (int)hipEventCreateWithFlags(ev, hipEventDisableTiming); }
+  int event_destroy(Event ev) const { return (int)hipEventDestroy(ev); }
+  int event_record(Event ev, Stream s) const { return (int)hipEventRecord(ev, s); }
+  int event_query(Event ev) const { return (int)hipEventQuery(ev); }
+  int event_synchronize(Event ev) const { return (int)hipEventSynchronize(ev); }
+  int stream_wait_event(Stream s, Event ev) const { return (int)hipStreamWaitEvent(s, ev, 0); }
+  int stream_synchronize(Stream s) const { return (int)hipStreamSynchronize(s); }
+  int device_synchronize() const { return (int)hipDeviceSynchronize(); }
+  void clear_last_error() const { (void)hipGetLastError(); }
+  int alloc_block(void** out, size_t bytes) const { return (int)pool_alloc(*device, out, bytes); }
+  void free_block(void* p) const { pool_free(*device, p); }
+};
+
 }  // namespace interpn_abi
 
-struct interpn_hip_interp {
+struct interpn_hip_interp : scratch_slots::Table<interpn_abi::HipRuntime> {
   interpn::GridDesc desc;
   int device = 0;
   void* vals_owned = nullptr;   // device copy of vals when created from host memory
@@ -141,16 +169,7 @@ struct interpn_hip_interp {
   unsigned long long* finish_word_dev = nullptr;  // ... as the device sees it (the status kernel's target), or null
   std::mutex finish_mu;
   std::mutex host_mu;  // host-pointer evaluations on one handle share its two lanes: serialised
-  // Caller streams that device-pointer work was enqueued on: interpn_hip_destroy waits for exactly
-  // these (and its own lane streams) instead of stalling the whole device.  Remembering a stream
-  // puts nothing on it: a launch costs no command beyond its kernels, and destroy waits for
-  // whatever the stream holds by then.  `sync_device_at_destroy` is set for launches that could
-  // not be marked (a stream under capture, more than kMaxMarks streams) and for streams that
-  // cannot be waited for any more (destroyed by the caller).
-  static constexpr size_t kMaxMarks = 16;
-  std::mutex marks_mu;
-  std::vector<hipStream_t> marks;
-  bool sync_device_at_destroy = false;
+  // (marks, sync_device_at_destroy: the caller streams interpn_hip_destroy waits for — scratch_slots.h)
   // Host-evaluation workspace (lazily allocated, reused across calls): two pipeline lanes so
   // that the upload of one chunk overlaps the download of the previous one.
   struct HostLane {
@@ -177,29 +196,12 @@ struct interpn_hip_interp {
   // used one.  `bin_mu` guards the slot list and the
   // per-handle report fields (desc.last_binned, desc.tag of a binned launch); the launches
   // themselves are enqueued outside it.
-  static constexpr size_t kMaxBinSlots = 4;
-  struct BinSlot {
-    void* scratch = nullptr;
-    size_t bytes = 0;
-    hipEvent_t event = nullptr;
-    bool recorded = false;       // `event` has been recorded behind the block's last use
-    bool unmarked = false;       // the last use may be in flight on `last_stream` with no event behind it yet (settle_slot)
-    bool busy = false;           // a host thread is enqueueing into this block right now
-    hipStream_t last_stream = nullptr;
-    unsigned long long stamp = 0;  // use counter value of the last use (LRU)
-    bool totals_clean = false;     // the block's bin counters are zero (left so by the last complete sort's scan)
-    // the block's first sweep_work_bytes() are a SweepWork a complete sweep launch left behind (round counters zero, the
-    // measured period kept for the next launch).  The two invariants exclude each other: the period word lies inside the
-    // sort's histogram (totals[291]), so whichever path uses a block clears the other path's flag.
-    bool sweep_clean = false;
-    hipEvent_t stage[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // option stage_timing: start | hist | scan | scatter | kernel
-    bool staged = false;           // the last use recorded them (single slice)
-  };
-  std::mutex bin_mu;
-  std::vector<BinSlot> bin_slots;  // capacity kMaxBinSlots from the start: evaluations hold pointers to elements outside the lock
-  unsigned long long bin_uses = 0;
-  interpn_hip_interp() { bin_slots.reserve(kMaxBinSlots); }
-  std::atomic<long long> evals_binned{0}, evals_in_place{0}, evals_sweep{0}, scratch_allocs{0};
+  // The blocks themselves (BinSlot, bin_mu, bin_slots, bin_uses, scratch_allocs) and the rules are scratch_slots.h's.
+  interpn_hip_interp() {
+    rt.device = &device;
+    word_in_block = &sampling.last_word;
+  }
+  std::atomic<long long> evals_binned{0}, evals_in_place{0}, evals_sweep{0};
   // The device-side sample in front of automatic sweep launches (abi_sweep.hip; guarded by bin_mu).  Thinning it out
   // (option sweep_probe = 2): the sampling kernel also stores (seq << 1 | coherent) into the pinned word `host`; the host
   // looks at it before the next launch — no synchronisation, a verdict that has not landed yet simply is not known yet.

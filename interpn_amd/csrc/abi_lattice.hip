@@ -10,27 +10,10 @@ namespace interpn_abi {
 
 using Slot = interpn_hip_interp::BinSlot;
 
-// Under graph capture no event of a block may be queried, waited for or recorded (the captured launch may replay at any
-// later time): take a block that is large enough without any of that.  The caller keeps other streams away from the
-// handle while such a graph replays (include/interpn_hip.h).
-Slot* take_slot_captured(interpn_hip_interp* h, size_t need, hipStream_t stream) {
-  std::lock_guard<std::mutex> lk(h->bin_mu);
-  Slot* pick = nullptr;
-  for (auto& sl : h->bin_slots) {
-    if (sl.busy || sl.bytes < need) continue;
-    if (!pick || sl.last_stream == stream) pick = &sl;
-  }
-  if (pick) {
-    pick->busy = true;
-    pick->stamp = ++h->bin_uses;
-  }
-  return pick;
-}
+// Under graph capture no event of a block may be queried, waited for or recorded: scratch_slots.h takes a block without.
+Slot* take_slot_captured(interpn_hip_interp* h, size_t need, hipStream_t stream) { return scratch_slots::take_slot_captured(*h, need, stream); }
 
-void release_slot_captured(interpn_hip_interp* h, Slot* slot) {
-  std::lock_guard<std::mutex> lk(h->bin_mu);
-  slot->busy = false;
-}
+void release_slot_captured(interpn_hip_interp* h, Slot* slot) { scratch_slots::release_slot_captured(*h, slot); }
 
 // The block's contents are the caller's now: the sort's and the sweep's invariants about it are gone.
 void claim_slot(interpn_hip_interp* h, Slot* slot) {
@@ -43,37 +26,11 @@ void claim_slot(interpn_hip_interp* h, Slot* slot) {
   if (word && word >= base && word < base + slot->bytes) h->sampling.last_word = nullptr;
 }
 
+// `nstreams` blocks of at least `need` bytes (scratch_slots.h: reserve_blocks; also what interpn_hip_reserve ends in).
 int reserve_slots(interpn_hip_interp* h, size_t need, int nstreams) {
-  std::lock_guard<std::mutex> lk(h->bin_mu);
-  int have = 0;
-  for (auto& sl : h->bin_slots)
-    if (sl.bytes >= need) ++have;
-  for (auto& sl : h->bin_slots) {  // grow idle blocks that are too small first, then add new ones (as interpn_hip_reserve)
-    if (have >= nstreams) break;
-    if (sl.bytes >= need || sl.busy || !settle_slot(h, sl)) continue;
-    if (sl.recorded) HIP_TRY(hipEventSynchronize(sl.event));
-    pool_free(h->device, sl.scratch);
-    h->sampling.last_word = nullptr;
-    sl.scratch = nullptr;
-    sl.bytes = 0;
-    sl.totals_clean = false;
-    sl.sweep_clean = false;
-    sl.recorded = false;
-    if (pool_alloc(h->device, &sl.scratch, need) != hipSuccess) { (void)hipGetLastError(); sl.scratch = nullptr; return INTERPN_HIP_ERR_OUT_OF_MEMORY; }
-    sl.bytes = need;
-    h->scratch_allocs.fetch_add(1);
-    ++have;
-  }
-  while (have < nstreams && h->bin_slots.size() < interpn_hip_interp::kMaxBinSlots) {
-    Slot sl;
-    HIP_TRY(hipEventCreateWithFlags(&sl.event, hipEventDisableTiming));
-    if (pool_alloc(h->device, &sl.scratch, need) != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(sl.event); return INTERPN_HIP_ERR_OUT_OF_MEMORY; }
-    sl.bytes = need;
-    h->scratch_allocs.fetch_add(1);
-    h->bin_slots.push_back(sl);
-    ++have;
-  }
-  return have >= nstreams ? INTERPN_HIP_OK : INTERPN_HIP_ERR_OUT_OF_MEMORY;
+  int rt_error = 0;
+  const int st = scratch_slots::reserve_blocks(*h, need, nstreams, &rt_error);
+  return st < 0 ? hip_fail((hipError_t)rt_error) : st;
 }
 
 }  // namespace interpn_abi

@@ -58,26 +58,6 @@ hipError_t launch_any(const GridDesc& g, const void* const* obs, void* out, size
 // No allocation, copy, synchronisation or stream command: the stream is noted, and
 // interpn_hip_destroy waits for it.  A stream under capture is never touched, so eval_device stays
 // graph-capturable.
-void mark_stream(interpn_hip_interp* h, hipStream_t stream) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) {
-    (void)hipGetLastError();
-    std::lock_guard<std::mutex> lk(h->marks_mu);
-    h->sync_device_at_destroy = true;
-    return;
-  }
-  std::lock_guard<std::mutex> lk(h->marks_mu);
-  if (cs != hipStreamCaptureStatusNone) {
-    h->sync_device_at_destroy = true;  // the graph may replay this launch at any later time
-    return;
-  }
-  for (hipStream_t m : h->marks)
-    if (m == stream) return;
-  if (h->marks.size() >= interpn_hip_interp::kMaxMarks) {
-    h->sync_device_at_destroy = true;
-    return;
-  }
-  h->marks.push_back(stream);
-}
+void mark_stream(interpn_hip_interp* h, hipStream_t stream) { scratch_slots::mark_stream(*h, stream); }
 
 }  // namespace interpn_abi

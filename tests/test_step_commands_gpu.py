@@ -313,3 +313,181 @@ def test_capture_is_not_touched(oracle, monkeypatch, which):
         del graph
     finally:
         it.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The previous use REALLY still in flight.  In the cases above a kernel of a few microseconds has long finished when the
+# other stream takes its block (the host side of a call is ~45 us), so they would pass without the wait in take_bin_slot or
+# the stream waits in interpn_hip_destroy.  Here a device-side delay of at least 0.5 s sits in front of the library's launch,
+# and the host looks 50 ms later: a 10x margin, a condition of the test and not a measurement.
+
+STALL_S = 0.5
+LOOK_S = 0.05
+_cycles_per_s = []
+
+
+def _stall(torch):
+    """Enqueues a delay on the current stream and returns the pair of events around it; `_stalled_long_enough` asserts
+    afterwards that it lasted STALL_S.  The cycle count is calibrated once, with two events."""
+    if not _cycles_per_s:
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda._sleep(1_000_000)  # (first launch of the kernel: not timed)
+        torch.cuda.synchronize()
+        t0.record()
+        torch.cuda._sleep(20_000_000)
+        t1.record()
+        t1.synchronize()
+        _cycles_per_s.append(20_000_000 / (t0.elapsed_time(t1) * 1e-3))
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    torch.cuda._sleep(int(1.5 * STALL_S * _cycles_per_s[0]))
+    t1.record()
+    return t0, t1
+
+
+def _stalled_long_enough(pair):
+    pair[1].synchronize()
+    assert pair[0].elapsed_time(pair[1]) >= STALL_S * 1e3, pair[0].elapsed_time(pair[1])
+
+
+@pytest.mark.parametrize("which", ["sweep", "sorted"])
+def test_other_stream_waits_for_a_stalled_use(oracle, monkeypatch, which):
+    """ONE block.  Stream A is stalled and then launches into the block; stream B launches with allocation forbidden, so it
+    gets A's block and must wait for A's use on the device: 50 ms later B's event is not complete (A is still stalled), the
+    launch took the forced path, and there is still one block.  The control, same stall: a launch on B through a SECOND
+    handle (its own block) in front of that has its event complete by then — the runtime does run the two streams side by
+    side, so the pending event is the library's wait and nothing else.  Afterwards every result has the oracle's bits."""
+    import time
+
+    import torch
+
+    import interpn_amd
+
+    dev = torch.device("cuda:0")
+    case, it, path, counter = _open(which, interpn_amd, monkeypatch)
+    _, other, _, _ = _open(which, interpn_amd, monkeypatch)
+    n = case.obs[0].size
+    want = run_oracle(oracle, case, True)
+    try:
+        a, b = torch.cuda.Stream(), torch.cuda.Stream()
+        obs = [torch.from_numpy(o).to(dev) for o in case.obs]
+        outs = torch.zeros((4, n), dtype=torch.float64, device=dev)
+        with torch.cuda.stream(a):
+            it.eval_tensors(obs, outs[0])  # makes the one block
+        with torch.cuda.stream(b):
+            other.eval_tensors(obs, outs[1])  # ... and the second handle's
+        torch.cuda.synchronize()
+        outs.zero_()
+        torch.cuda.synchronize()
+        e_control, e_b = torch.cuda.Event(), torch.cuda.Event()
+        with torch.cuda.stream(a):
+            stall = _stall(torch)
+            it.eval_tensors(obs, outs[0], no_alloc=True)
+            assert it.last_path == path
+        with torch.cuda.stream(b):
+            other.eval_tensors(obs, outs[1], no_alloc=True)
+            assert other.last_path == path
+            e_control.record()
+            it.eval_tensors(obs, outs[2], no_alloc=True)
+            taken = (it.last_path, it.last_path_reason)
+            e_b.record()
+        time.sleep(LOOK_S)
+        control_done, b_done, a_done = e_control.query(), e_b.query(), stall[1].query()
+        allocs = it.get_option("scratch_allocs")
+        a.synchronize()
+        b.synchronize()
+        _stalled_long_enough(stall)
+        assert not a_done  # the stall was still on when the host looked
+        assert control_done, "the runtime serialised the two streams: the next assertion would show nothing"
+        assert not b_done, "stream B did not wait for the stalled use of the block it was handed"
+        assert taken[0] == path, taken
+        assert allocs == 1 and it.get_option(counter) == 3
+        got = outs.cpu().numpy()
+        for k in range(3):
+            _same_bits(got[k], want, (which, k))
+    finally:
+        it.close()
+        other.close()
+
+
+@pytest.mark.parametrize("which", ["sweep", "sorted"])
+def test_close_waits_for_a_stalled_stream(oracle, monkeypatch, which):
+    """A stalled side stream, three launches, an event, `close()`: when `close()` returns the event is complete (it has waited
+    at least the stall out), a second handle that takes the blocks from the pool gives the oracle's bits, and so do the three
+    results."""
+    import torch
+
+    import interpn_amd
+
+    dev = torch.device("cuda:0")
+    case, it, path, counter = _open(which, interpn_amd, monkeypatch)
+    n = case.obs[0].size
+    want = run_oracle(oracle, case, True)
+    side = torch.cuda.Stream()
+    obs = [torch.from_numpy(o).to(dev) for o in case.obs]
+    outs = torch.zeros((3, n), dtype=torch.float64, device=dev)
+    ev = torch.cuda.Event()
+    torch.cuda.synchronize()
+    try:
+        with torch.cuda.stream(side):
+            stall = _stall(torch)
+            for k in range(3):
+                it.eval_tensors(obs, outs[k])
+                assert it.last_path == path
+            ev.record()
+        assert not ev.query()  # (the stall is on)
+    finally:
+        it.close()
+    assert ev.query(), "close() returned with the handle's work still in flight"
+    _stalled_long_enough(stall)
+    _, it2, path2, _ = _open(which, interpn_amd, monkeypatch)
+    try:
+        got2 = it2.eval_tensors(obs)
+        assert it2.last_path == path2
+        it2.finish()
+        _same_bits(got2.cpu().numpy(), want, which)
+    finally:
+        it2.close()
+    got = outs.cpu().numpy()
+    for k in range(3):
+        _same_bits(got[k], want, (which, k))
+
+
+def test_reserve_regrows_only_after_the_stalled_use(oracle, monkeypatch):
+    """The sorted path's block grows with the batch.  A stalled stream, a 5 000-point launch, an event; `reserve(50_000, 1)`
+    must regrow the block — free it and allocate a larger one — and may do so only once the launch has run: on return there
+    are two allocations and the event is complete.  The result has the oracle's bits."""
+    import torch
+
+    import interpn_amd
+
+    dev = torch.device("cuda:0")
+    case, it, path, counter = _open("sorted", interpn_amd, monkeypatch)
+    n = case.obs[0].size
+    want = run_oracle(oracle, case, True)
+    try:
+        side = torch.cuda.Stream()
+        obs = [torch.from_numpy(o).to(dev) for o in case.obs]
+        out = torch.zeros(n, dtype=torch.float64, device=dev)
+        ev = torch.cuda.Event()
+        with torch.cuda.stream(side):
+            it.eval_tensors(obs, out)  # makes the block
+        torch.cuda.synchronize()
+        out.zero_()
+        torch.cuda.synchronize()
+        assert it.get_option("scratch_allocs") == 1
+        with torch.cuda.stream(side):
+            stall = _stall(torch)
+            it.eval_tensors(obs, out, no_alloc=True)
+            assert it.last_path == path
+            ev.record()
+        assert not ev.query()  # (the stall is on)
+        it.reserve(50_000, 1)
+        done = ev.query()
+        assert it.get_option("scratch_allocs") == 2
+        assert done, "reserve freed the block with its last use still in flight"
+        _stalled_long_enough(stall)
+        it.finish()
+        _same_bits(out.cpu().numpy(), want)
+    finally:
+        it.close()
