@@ -12,6 +12,7 @@ outputs of the reference itself.  They freeze
       (oracle/exact_rational.py: `fractions.Fraction`, tensor-product form — no rounding, and no
       code shared with the C++ oracle) rounded once to f64, and the rounding-error scale
       sum|w||v| + sum_d (|x_d| + max|g_d|) |dI/dx_d| the tests multiply by 4 u,
+  (d) the same as (b) and (c) on the anisotropic workload (tests/helpers.py::anisotropic_case),
 so that the oracle cannot drift silently and the GPU path can be checked — against the oracle AND
 against something that is not the oracle — on a box where only the committed data travels.  Run from the repository root:  python tests/golden/make_golden.py
 """
@@ -25,7 +26,7 @@ sys.path.insert(0, ROOT)
 
 from oracle import exact_rational, pyoracle  # noqa: E402
 from tests import kat  # noqa: E402
-from tests.helpers import run_oracle, synthetic_case  # noqa: E402
+from tests.helpers import anisotropic_case, run_oracle, synthetic_case  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 
@@ -79,7 +80,24 @@ def main():
                     blob[f"{c.name}/{key}"] = v
                 print(c.name, flush=True)
     np.savez_compressed(os.path.join(OUT, "random_cases.npz"), **blob)
-    for f in ("kat_cases.npz", "random_cases.npz"):
+    # (d) the anisotropic workload (tests/helpers.py::anisotropic_case: per-axis origin, scale and spacing), with the
+    #     same contents as (b) and (c): the cases of tests/test_anisotropic_cpu.py
+    blob = {}
+    for dtype in (np.float64, np.float32):
+        for m, lin in (("linear", False), ("cubic", False), ("cubic", True)):
+            for k in ("regular", "rectilinear"):
+                for shape in ([9, 7], [6, 5, 7], [5, 6, 4, 5]):
+                    c = anisotropic_case(m, k, shape, 120, 7100 + len(shape), dtype, linearize=lin)
+                    c.name = f"aniso_{m}_{k}_N{len(shape)}_{'f64' if dtype == np.float64 else 'f32'}_lin{int(lin)}"
+                    ex = exact_rational.evaluate_with_condition(m, k, c.grids, c.vals, c.obs, lin, c.starts, c.steps)
+                    extra = {"oracle_fma1": run_oracle(pyoracle, c, True), "oracle_fma0": run_oracle(pyoracle, c, False),
+                             "exact": np.array([float(v) for v, _ in ex]),
+                             "exact_scale": np.array([float(sc) for _, sc in ex])}
+                    for key, v in pack(c, extra).items():
+                        blob[f"{c.name}/{key}"] = v
+                    print(c.name, flush=True)
+    np.savez_compressed(os.path.join(OUT, "anisotropic_cases.npz"), **blob)
+    for f in ("kat_cases.npz", "random_cases.npz", "anisotropic_cases.npz"):
         print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")
 
 

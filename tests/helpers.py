@@ -98,6 +98,77 @@ def synthetic_case(method, kind, n, npts_axis, nobs, seed, dtype=np.float64, lin
                 linearize=linearize)
 
 
+# (start, step) of axis d of `anisotropic_case`: origins large against the step (d = 0, 2), steps that are no binary
+# fraction (1, 3), one that is (4), and eight decades between the smallest and the largest step.
+ANISO_AXES = ((1000.25, 0.0375), (-3e-3, 7e-4), (-5e4, 1.3e3), (0.5, 1.0 / 3.0), (7.0, 2.0 ** -7), (-0.125, 11.0))
+
+
+def anisotropic_axis(d, n, kind, dtype, rng):
+    """Axis d of `anisotropic_case`, n nodes.  Regular: start + step * arange(n).  Rectilinear: the same ends, the
+    intervals by d % 3 — growing geometrically (x1.7 per interval, ~70 between first and last), shrinking (x0.55,
+    ~1/120), or equal with a cluster of intervals at 1e-3 of the others in the middle (two; twenty from 24 nodes on) —
+    each scaled by 1 + 0.2 (U - 0.5).  Axes of more than 9 nodes spread the same total ratio over their intervals."""
+    start, step = ANISO_AXES[d % len(ANISO_AXES)]
+    step *= 2.0 ** (d // len(ANISO_AXES))
+    if kind == "regular":
+        g = (start + step * np.arange(n)).astype(dtype)
+    else:
+        m = n - 1  # intervals
+        mode = d % 3
+        if mode < 2:
+            q = (1.7, 0.55)[mode]
+            if m > 8:
+                q = q ** (8.0 / (m - 1))
+            h = q ** np.arange(m)
+        else:
+            h = np.ones(m)
+            short = 20 if n >= 24 else min(2, m - 1)
+            lo = (m - short) // 2
+            h[lo:lo + short] = 1e-3
+        h = h * (1.0 + 0.2 * (rng.random(m) - 0.5))
+        h *= step * m / h.sum()
+        g = start + np.concatenate([[0.0], np.cumsum(h)])
+        g[-1] = start + step * m
+        g = g.astype(dtype)
+    assert np.all(np.diff(g) > 0), (d, n, kind, np.dtype(dtype).name)
+    return g
+
+
+def anisotropic_points(g, count, rng, dtype, extrap=0.2):
+    """`count` coordinates on axis g by the point rule of `anisotropic_case`: exact nodes (12 at most), both ends and
+    their floating-point neighbours outside the grid; of the rest one half cell-uniform (a cell drawn uniformly, then a
+    position in it: short intervals are hit as often as long ones) and one half uniform over the extent widened by
+    `extrap` on each side; shuffled."""
+    g64 = g.astype(np.float64)
+    nodes = g[rng.choice(g.size, min(g.size, 12), replace=False)]
+    special = np.concatenate([nodes, [g[0], g[-1], np.nextafter(g[0], dtype(-np.inf)), np.nextafter(g[-1], dtype(np.inf))]])
+    special = special[:max(0, count - 2)].astype(dtype)
+    rest = count - special.size
+    ncell = rest // 2
+    c = rng.integers(0, g.size - 1, ncell)
+    in_cell = (g64[c] + rng.random(ncell) * (g64[c + 1] - g64[c])).astype(dtype)
+    w = (g64[-1] - g64[0]) * extrap
+    wide = rng.uniform(g64[0] - w, g64[-1] + w, rest - ncell).astype(dtype)
+    x = np.concatenate([special, in_cell, wide]).astype(dtype)
+    rng.shuffle(x)
+    return x
+
+
+def anisotropic_case(method, kind, shape, nobs, seed, dtype=np.float64, linearize=False, extrap=0.2):
+    """The second workload: every axis with its own origin, scale and spacing (ANISO_AXES, `anisotropic_axis`), so that
+    a per-axis quantity taken from the wrong axis, or a search that only works on near-uniform axes, changes the result
+    — on `synthetic_case` neither does.  vals U(-1, 1); points by `anisotropic_points`, shuffled per axis."""
+    from tests.kat import Case
+
+    rng = np.random.default_rng(seed)
+    dtype = np.dtype(dtype).type
+    grids = [anisotropic_axis(d, shape[d], kind, dtype, rng) for d in range(len(shape))]
+    vals = rng.uniform(-1.0, 1.0, int(np.prod(shape))).astype(dtype)
+    obs = [anisotropic_points(g, nobs, rng, dtype, extrap) for g in grids]
+    return Case(f"aniso_{method}_{kind}_N{len(shape)}", method, kind, grids, vals, obs, np.zeros(nobs, dtype=dtype), 0.0,
+                linearize=linearize)
+
+
 def rel_err(a, b):
     """|a-b| / max(|b|, 1) — the reference's normalisation (test/test_multicubic_regular.py:97-100)."""
     a = np.asarray(a, dtype=np.float64)

@@ -35,13 +35,15 @@ def load_cases(fname):
 
 KAT = load_cases("kat_cases.npz")
 RND = load_cases("random_cases.npz")
+# the anisotropic workload (tests/helpers.py::anisotropic_case): per-axis origin, scale and spacing
+ANI = load_cases("anisotropic_cases.npz")
 
 
 def same(a, b):
     return bool(np.all((a == b) | (np.isnan(a) & np.isnan(b))))
 
 
-@pytest.mark.parametrize("case", KAT + RND, ids=lambda c: c.name)
+@pytest.mark.parametrize("case", KAT + RND + ANI, ids=lambda c: c.name)
 def test_oracle_reproduces_golden(oracle, case):
     assert same(run_oracle(oracle, case, True), case.extra["oracle_fma1"])
     assert same(run_oracle(oracle, case, False), case.extra["oracle_fma0"])
@@ -52,7 +54,8 @@ def test_oracle_reproduces_golden(oracle, case):
 # in floating point with unit round-off u = eps/2 of its dtype lies within EXACT_K * u * scale of the
 # exact value, scale = sum|w||v| + sum_d (|x_d| + max|g_d|) |dI/dx_d| per point (stored with the
 # fixture).  Measured: the oracle's worst ratio over all 60 workloads is 3.5 (cubic rectilinear:
-# ~10 divides per node); typical 0.05.  A transcription error in the Hermite c3 term
+# ~10 divides per node); typical 0.05; over the 36 anisotropic workloads 0.03 (their scale carries
+# |x_d| / h_d, up to 3e4, while x - g[i] is exact that close to a node).  A transcription error in the Hermite c3 term
 # (multicubic/mod.rs:72-91) changes results by ~1e-2 * scale: 13 orders of magnitude above this.
 EXACT_K = 16.0
 
@@ -64,17 +67,17 @@ def within_exact_bound(got, case):
 
 
 @pytest.mark.parametrize("fma", [True, False], ids=["fma", "nofma"])
-@pytest.mark.parametrize("case", RND, ids=lambda c: c.name)
+@pytest.mark.parametrize("case", RND + ANI, ids=lambda c: c.name)
 def test_oracle_within_exact_rational_bound(oracle, case, fma):
     ok, worst = within_exact_bound(run_oracle(oracle, case, fma), case)
     assert np.all(ok), (case.name, worst)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", RND, ids=lambda c: c.name)
+@pytest.mark.parametrize("case", RND + ANI, ids=lambda c: c.name)
 def test_hip_within_exact_rational_bound(case):
     """The one check of the HIP path that does not pass through the builder's C++ restatement:
-    every linear and cubic workload of random_cases.npz against the exact interpolant."""
+    every linear and cubic workload of random_cases.npz and anisotropic_cases.npz against the exact interpolant."""
     got = run_hip_raw(case)
     ok, worst = within_exact_bound(got, case)
     assert np.all(ok), (case.name, worst)
@@ -91,7 +94,7 @@ def test_hip_within_exact_rational_bound_without_fma():
     lib = _lib.load()
     prev = lib.interpn_hip_set_fma(0)
     try:
-        for case in RND:
+        for case in RND + ANI:
             ok, worst = within_exact_bound(run_hip_raw(case), case)
             assert np.all(ok), (case.name, worst)
     finally:
@@ -99,7 +102,7 @@ def test_hip_within_exact_rational_bound_without_fma():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", KAT + RND, ids=lambda c: c.name)
+@pytest.mark.parametrize("case", KAT + RND + ANI, ids=lambda c: c.name)
 def test_hip_reproduces_golden(case):
     got = run_hip_raw(case)
     assert got.dtype == case.vals.dtype
@@ -113,7 +116,7 @@ def test_hip_reproduces_golden_without_fma():
     lib = _lib.load()
     prev = lib.interpn_hip_set_fma(0)
     try:
-        for case in RND:
+        for case in RND + ANI:
             assert same(run_hip_raw(case), case.extra["oracle_fma0"]), case.name
     finally:
         lib.interpn_hip_set_fma(prev)
