@@ -169,6 +169,83 @@ def anisotropic_case(method, kind, shape, nobs, seed, dtype=np.float64, lineariz
                 linearize=linearize)
 
 
+def poison_count(shape, method):
+    """How many nodes `poison_table` makes non-finite ("nan", "mixed"): with F nodes in a point's footprint (2^N
+    multilinear, 4^N multicubic, 1 nearest) a share 1 - 0.5^(1/F) of the table leaves about half the points clean."""
+    size = int(np.prod(shape))
+    f = {"linear": 2.0, "cubic": 4.0, "nearest": 1.0}[method] ** len(shape)
+    return max(1, int(round(size * (1.0 - 0.5 ** (1.0 / f)))))
+
+
+def poison_table(vals, shape, method, seed, kind):
+    """A copy of the table `vals` with non-finite nodes; every other node keeps its value.  kind "nan": `poison_count`
+    distinct nodes, drawn by a seeded `rng.choice`, are NaN.  "mixed": the same nodes, each NaN, +inf or -inf at random.
+    "plane": every node with index 3 along the shape's longest axis (the first of them; it needs n >= 5) is NaN — for
+    multicubic the fourth node of that axis's first cell, which the saturated cell does not use."""
+    out = np.array(vals, copy=True)
+    assert out.size == int(np.prod(shape))
+    if kind == "plane":
+        d = int(np.argmax(shape))
+        assert shape[d] >= 5, shape
+        index = [slice(None)] * len(shape)
+        index[d] = 3
+        out.reshape(shape)[tuple(index)] = np.nan
+        return out
+    assert kind in ("nan", "mixed"), kind
+    rng = np.random.default_rng(seed)
+    where = rng.choice(out.size, poison_count(shape, method), replace=False)
+    if kind == "nan":
+        out[where] = np.nan
+    else:
+        out[where] = rng.choice(np.array([np.nan, np.inf, -np.inf]), where.size).astype(out.dtype)
+    return out
+
+
+def footprint_cells(case):
+    """Per axis the cell index c of every point of `case`: j = floor((x - start) / step) in the element type (regular)
+    or (number of nodes < x) - 1 (rectilinear), clamped to [0, n - 2]."""
+    dt = case.vals.dtype.type
+    cells = []
+    for d, (g, x) in enumerate(zip(case.grids, case.obs)):
+        x = np.asarray(x, dtype=dt)
+        if case.kind == "regular":
+            j = np.floor((x - dt(case.starts[d])) / dt(case.steps[d])).astype(np.float64)
+        else:
+            j = np.searchsorted(np.asarray(g, dtype=dt), x, side="left").astype(np.float64) - 1.0
+        cells.append(np.clip(j, 0, g.size - 2).astype(np.int64))
+    return cells
+
+
+def footprint_poisoned(case):
+    """One bool per point of `case` (linear or cubic): the nodes its arithmetic touches include a non-finite one.  Along
+    an axis of n nodes with cell c (`footprint_cells`) multilinear uses nodes c and c + 1; multicubic uses c - 1 .. c + 2,
+    but 0 .. 2 in the first cell and n - 3 .. n - 1 in the last (the fourth node of a saturated cell is not used).  The
+    footprint is the product over the axes, for coordinates outside the grid too.  Written with numpy alone: a summed
+    table of the non-finite nodes, and the box sum of every point's footprint by inclusion and exclusion."""
+    assert case.method in ("linear", "cubic"), case.method
+    shape = case.dims
+    bad = ~np.isfinite(case.vals.reshape(shape))
+    summed = np.zeros([n + 1 for n in shape], dtype=np.int64)  # summed[i0, i1, ..] = bad nodes with index < i_d on every axis
+    summed[tuple(slice(1, None) for _ in shape)] = bad
+    for d in range(len(shape)):
+        summed = np.cumsum(summed, axis=d)
+    lo, hi = [], []  # the footprint's nodes along axis d: lo <= i < hi
+    for c, n in zip(footprint_cells(case), shape):
+        if case.method == "linear":
+            lo.append(c)
+            hi.append(c + 2)
+        else:
+            assert n >= 3, shape
+            lo.append(np.where(c == 0, 0, np.where(c == n - 2, n - 3, c - 1)))
+            hi.append(np.where(c == 0, 3, np.where(c == n - 2, n, c + 3)))
+    count = np.zeros(case.obs[0].size, dtype=np.int64)
+    for corner in range(1 << len(shape)):
+        index = tuple(hi[d] if (corner >> d) & 1 else lo[d] for d in range(len(shape)))
+        sign = -1 if (len(shape) - bin(corner).count("1")) & 1 else 1
+        count += sign * summed[index]
+    return count > 0
+
+
 def rel_err(a, b):
     """|a-b| / max(|b|, 1) — the reference's normalisation (test/test_multicubic_regular.py:97-100)."""
     a = np.asarray(a, dtype=np.float64)
