@@ -202,19 +202,88 @@ SORTED = [("sorted", S2, "11", "interpn::k_cubic_brick<"), ("sorted", S3, "44", 
 SORTED_NOBS = 5000  # more than one chunk of the sort (4096)
 
 
-def sorted_and_column_multicubic(case, want, fma, monkeypatch, form, layout, kernel):
+def sorted_handle(case, fma, monkeypatch, form, layout, options=None):
+    """A handle forced onto the sorted path (`binned`), its column form or the tiled kernel; then `options`, in order."""
     it = make_handle(case, fma, monkeypatch, layout)
     try:
         it.set_option("binned", 1)
         it.set_option("column", 1 if form == "column" else 0)
+        for k, v in (options or {}).items():
+            it.set_option(k, v)
+    except BaseException:
+        it.close()
+        raise
+    return it
+
+
+def assert_sorted(it, kernel):
+    """The evaluation just made sorted its points and ran `kernel` on them."""
+    assert it.last_path == "binned" and it.get_option("last_binned") == 1, (it.last_path, it.last_path_reason)
+    assert it.kernel_name().startswith(kernel), it.kernel_name()
+
+
+def sorted_and_column_multicubic(case, want, fma, monkeypatch, form, layout, kernel, options=None, run=None):
+    """`options`: a mapping of further handle options, set after `binned` / `column`.  `run(it, obs, want, kernel, what)`: makes
+    and checks each evaluation instead of the comparison with `want` alone (tests/test_unevenly_filled_bins_gpu.py)."""
+    it = sorted_handle(case, fma, monkeypatch, form, layout, options)
+    try:
         for deal in (1, 0):
             it.set_option("deal", deal)
+            if run is not None:
+                run(it, case.obs, want, kernel, (form, deal))
+                continue
             got = eval_device(it, case.obs)
-            assert it.last_path == "binned" and it.get_option("last_binned") == 1
-            assert it.kernel_name().startswith(kernel), it.kernel_name()
+            assert_sorted(it, kernel)
             assert_same(got, want, (form, deal))
     finally:
         it.close()
+
+
+# ---- 3b. the same path on skewed batches (tests/test_skewed_batches_cpu.py, tests/test_unevenly_filled_bins_gpu.py) ----------------------
+# The smallest grids at which the code in question exists.  [40, 37, 5, 4]: 37 x 34 = 1258 footprint cells for 1024 bins (key
+# shifts); [6, 7, 5, 6]: 30 class-pair bins; [41, 40, 5, 6]: 1560 (more than one per thread; the direct records scatter whatever
+# `scatter_staged` says); [20, 17, 33]: 304.
+SKEWED_FORMS = [("sorted", S2, "11", "interpn::k_cubic_brick<"), ("sorted", S3, "44", "interpn::k_cubic_brick<"),
+                ("sorted", S4, "11", "interpn::k_cubic_brick<"), ("sorted", [40, 37, 5, 4], "11", "interpn::k_cubic_brick<"),
+                ("column", [6, 7, 5, 6], "11", "interpn::k_cubic_column<"), ("column", [41, 40, 5, 6], "11", "interpn::k_cubic_column<"),
+                ("column", S3, "11", "interpn::k_cubic3_column<"), ("column", [20, 17, 33], "11", "interpn::k_cubic3_column<")]
+SKEWED_IDS = [f"{f}-{'x'.join(map(str, s))}" for f, s, _, _ in SKEWED_FORMS]
+SKEWED_SHAPES = [S2, S3, S4, [40, 37, 5, 4], [6, 7, 5, 6], [41, 40, 5, 6], [20, 17, 33]]
+COLUMN3_PART = 16 * 256  # points per part of the 3-D column kernel (k_cubic3_column.hip)
+
+
+def skewed_case(kind, shape, dtype, linearize=False):
+    """The anisotropic multicubic case on `shape` whose grids and table the skewed batches are evaluated on (its own points
+    are not used)."""
+    return make_case("cubic", kind, shape, dtype, nobs=16, linearize=linearize)
+
+
+def skewed_rng(shape, *salt):
+    return np.random.default_rng([7300, *shape, *salt])
+
+
+def swept_pairs(shape):
+    """The class pairs a `one_pair` batch is run on: all of them where there are at most 42, else 24 — the four corners, the
+    four edge midpoints and 16 by a seeded choice among the rest.  The bin's number on the device is key * mult % nbins, which
+    is not visible from here: running over pairs is what reaches the first and the last bins (the tail rule) anyway."""
+    m0, m1 = shape[0] - 1, shape[1] - 1
+    every = [(c0, c1) for c0 in range(m0) for c1 in range(m1)]
+    if len(every) <= 42:
+        return every
+    fixed = [(0, 0), (0, m1 - 1), (m0 - 1, 0), (m0 - 1, m1 - 1), (0, m1 // 2), (m0 - 1, m1 // 2), (m0 // 2, 0), (m0 // 2, m1 - 1)]
+    rest = [p for p in every if p not in fixed]
+    pick = np.random.default_rng([7301, *shape]).choice(len(rest), 16, replace=False)
+    return fixed + [rest[int(k)] for k in sorted(pick)]
+
+
+def heavy_pairs(shape):
+    """Low corner, high corner and one interior pair."""
+    m0, m1 = shape[0] - 1, shape[1] - 1
+    return [(0, 0), (m0 - 1, m1 - 1), (m0 // 2, m1 // 2)]
+
+
+def with_obs(case, obs):
+    return dataclasses.replace(case, obs=obs)
 
 
 # ---- 4. the sweep family: their grids, 3001 points = several ragged rounds --------------------------------------------------------------

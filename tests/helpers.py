@@ -3,6 +3,8 @@ dispatch of a `kat.Case` to either the oracle or the HIP path."""
 
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 
 
@@ -244,6 +246,158 @@ def footprint_poisoned(case):
         sign = -1 if (len(shape) - bin(corner).count("1")) & 1 else 1
         count += sign * summed[index]
     return count > 0
+
+
+def class_draw(g, c, count, rng, dtype, outside=False):
+    """`count` coordinates of saturation class `c` on the axis `g` (n nodes): the class is the clamped cell index of
+    `footprint_cells`, 0 .. n - 2; class 0 also holds everything below the grid, class n - 2 everything above it.  Inside
+    the grid the points are uniform in the cell [g[c], g[c + 1]] shrunk by a tenth of its width at each end, so that an
+    estimate of the class ((x - start) * scale on regular grids, the counting sort's) and the exact class agree.  With
+    `outside` the points of class 0 lie below g[0] and those of class n - 2 above g[-1], by 0.001 to 0.3 of the span."""
+    g64 = np.asarray(g, dtype=np.float64)
+    n = g64.size
+    assert 0 <= c <= n - 2, (c, n)
+    u = rng.random(count)
+    if outside:
+        assert c in (0, n - 2), (c, n)
+        off = (g64[-1] - g64[0]) * (0.001 + 0.299 * u)
+        x = g64[0] - off if c == 0 else g64[-1] + off
+    else:
+        w = g64[c + 1] - g64[c]
+        x = g64[c] + w * (0.1 + 0.8 * u)
+    return x.astype(dtype)
+
+
+def class_pairs(case):
+    """Every pair of saturation classes of axes 0 and 1: the bins of the sorted multicubic path, in C order."""
+    return [(c0, c1) for c0 in range(case.dims[0] - 1) for c1 in range(case.dims[1] - 1)]
+
+
+SKEWED_CHUNK = 4096  # points per workgroup of the sort's scatter kernels
+
+
+def skewed_obs(case, dist, rng, **kw):
+    """New observation arrays for `case` (one per axis, the case's element type) that are NOT spread evenly over the bins
+    of the sorted multicubic path.  The sort key is the pair of saturation classes of axes 0 and 1 (`class_pairs`,
+    `class_draw`); axes that a distribution does not name keep the point rule of `anisotropic_points`.  `count` is the
+    number of points wherever the distribution does not fix it.
+
+      one_pair(pair, count)       every point in the class pair `pair` (inside the grid);
+      heavy(pair, c)              one point in every class pair, `c` points in all in `pair` (its own among them): P - 1 + c
+                                  points for P pairs, shuffled;
+      one_each(k[, empty])        exactly k points per class pair, shuffled; the pair `empty` gets none;
+      ordered(count)              a batch by the point rule, stably sorted by (c0, c1);
+      reversed(count)             the same batch in reverse order;
+      striped(pairs, count)       every chunk of SKEWED_CHUNK points holds points of one pair, pairs[0] and pairs[1] in turn;
+      outside0(count)             every point outside the grid along axis 0, below or above at random;
+      one_outside                 3000 points of class 0 of axis 0 inside the grid and one below it, at index 1234;
+      local_one(pair, c2[, c3], count)  every point in `pair`, of class c2 on axis 2 (and c3 on axis 3);
+      local_ends(pair, count)     every point in `pair`, of the first or the last class of axis 2 at random;
+      identical(which, count)     one point repeated: "interior" (inside an interior cell of every axis), "node" (a grid
+                                  node on every axis), "beyond" (past the high corner on every axis);
+      on_nodes(count)             every coordinate a node of its axis, drawn uniformly;
+      nan0(count)                 a batch by the point rule, NaN on axis 0 for every point;
+      half_nan0(count)            ... NaN on axis 0 for every second point of the second half."""
+    grids, dt = case.grids, case.vals.dtype.type
+    n = len(grids)
+    pairs = class_pairs(case)
+
+    def rule(count, skip=()):
+        return [None if d in skip else anisotropic_points(grids[d], count, rng, dt) for d in range(n)]
+
+    def in_pair(pair, count):
+        obs = rule(count, skip=(0, 1))
+        obs[0] = class_draw(grids[0], pair[0], count, rng, dt)
+        obs[1] = class_draw(grids[1], pair[1], count, rng, dt)
+        return obs
+
+    def by_pair(counts):
+        """counts[p] points in pair p, shuffled as a whole"""
+        which = np.repeat(np.arange(len(pairs)), counts)
+        rng.shuffle(which)
+        obs = rule(which.size, skip=(0, 1))
+        obs[0], obs[1] = np.empty(which.size, dtype=dt), np.empty(which.size, dtype=dt)
+        for p, (c0, c1) in enumerate(pairs):
+            at = which == p
+            obs[0][at] = class_draw(grids[0], c0, int(at.sum()), rng, dt)
+            obs[1][at] = class_draw(grids[1], c1, int(at.sum()), rng, dt)
+        return obs
+
+    if dist == "one_pair":
+        return in_pair(kw["pair"], kw["count"])
+    if dist == "heavy":
+        counts = np.ones(len(pairs), dtype=np.int64)
+        counts[pairs.index(tuple(kw["pair"]))] = kw["c"]
+        return by_pair(counts)
+    if dist == "one_each":
+        counts = np.full(len(pairs), kw["k"], dtype=np.int64)
+        if kw.get("empty") is not None:
+            counts[pairs.index(tuple(kw["empty"]))] = 0
+        return by_pair(counts)
+    if dist in ("ordered", "reversed"):
+        obs = rule(kw["count"])
+        c = footprint_cells(dataclasses.replace(case, obs=obs))
+        order = np.lexsort((c[1], c[0]))  # stable; c0 is the primary key
+        if dist == "reversed":
+            order = order[::-1]
+        return [np.ascontiguousarray(o[order]) for o in obs]
+    if dist == "striped":
+        count = kw["count"]
+        obs = rule(count, skip=(0, 1))
+        obs[0], obs[1] = np.empty(count, dtype=dt), np.empty(count, dtype=dt)
+        for k, lo in enumerate(range(0, count, SKEWED_CHUNK)):
+            m = min(SKEWED_CHUNK, count - lo)
+            c0, c1 = kw["pairs"][k % 2]
+            obs[0][lo:lo + m] = class_draw(grids[0], c0, m, rng, dt)
+            obs[1][lo:lo + m] = class_draw(grids[1], c1, m, rng, dt)
+        return obs
+    if dist == "outside0":
+        count = kw["count"]
+        obs = rule(count, skip=(0,))
+        below = rng.random(count) < 0.5
+        below[:2] = (True, False)
+        obs[0] = np.where(below, class_draw(grids[0], 0, count, rng, dt, outside=True),
+                          class_draw(grids[0], grids[0].size - 2, count, rng, dt, outside=True)).astype(dt)
+        return obs
+    if dist == "one_outside":
+        obs = rule(3001, skip=(0,))
+        obs[0] = class_draw(grids[0], 0, 3001, rng, dt)
+        obs[0][1234] = class_draw(grids[0], 0, 1, rng, dt, outside=True)[0]
+        return obs
+    if dist == "local_one":
+        obs = in_pair(kw["pair"], kw["count"])
+        obs[2] = class_draw(grids[2], kw["c2"], kw["count"], rng, dt)
+        if kw.get("c3") is not None:
+            obs[3] = class_draw(grids[3], kw["c3"], kw["count"], rng, dt)
+        return obs
+    if dist == "local_ends":
+        count = kw["count"]
+        obs = in_pair(kw["pair"], count)
+        first = rng.random(count) < 0.5
+        first[:2] = (True, False)
+        obs[2] = np.where(first, class_draw(grids[2], 0, count, rng, dt), class_draw(grids[2], grids[2].size - 2, count, rng, dt)).astype(dt)
+        return obs
+    if dist == "identical":
+        which = kw["which"]
+        if which == "interior":
+            point = [class_draw(g, (g.size - 1) // 2, 1, rng, dt)[0] for g in grids]
+        elif which == "node":
+            point = [g[int(rng.integers(1, g.size - 1))] for g in grids]
+        else:
+            assert which == "beyond", which
+            point = [class_draw(g, g.size - 2, 1, rng, dt, outside=True)[0] for g in grids]
+        return [np.full(kw["count"], x, dtype=dt) for x in point]
+    if dist == "on_nodes":
+        return [np.ascontiguousarray(g[rng.integers(0, g.size, kw["count"])]) for g in grids]
+    if dist in ("nan0", "half_nan0"):
+        count = kw["count"]
+        obs = rule(count)
+        if dist == "nan0":
+            obs[0][:] = np.nan
+        else:
+            obs[0][count // 2::2] = np.nan
+        return obs
+    raise ValueError(dist)
 
 
 def rel_err(a, b):

@@ -1422,7 +1422,8 @@ def test_binned_multicubic_evaluation(oracle, monkeypatch, dtype, kind, axis, la
     sorted order dealt out to the XCDs or not, several tile layouts (forced: grids this small
     would stay on the C-order kernels, which have no binned form) — always the oracle's bits,
     NaN / inf coordinates and out-of-range points included.  src/multicubic/regular.rs:297-313 (a point's result depends
-    on its own coordinates only)."""
+    on its own coordinates only).  Every batch here is i.i.d. uniform over the grid's extent; batches that are not (one bin,
+    empty bins, the edges of a part) are tests/test_unevenly_filled_bins_gpu.py's."""
     import torch
 
     import interpn_amd
