@@ -604,6 +604,40 @@ int interpn_hip_fields_get_option(const interpn_hip_fields* fields, const char* 
 int interpn_hip_fields_layout(size_t elem_size, size_t ndims, const size_t* dims, size_t nfields, int* fields_per_line,
                               size_t* lines_per_point, size_t* table_bytes);
 
+/* Gradients of a field set — the K values AND their K x N Jacobian at every point in one call: Newton inversion of an
+ * equation-of-state table (K = N), the velocity-gradient tensor of a vector field, `backward` through every channel.
+ *
+ * Definition  for every field f and point i, out[f * out_stride + i] is what interpn_hip_fields_eval_* returns for field f,
+ *           and grad[(f * ndims + d) * grad_stride + i] is component d of what interpn_hip_eval_grad_* returns for the single
+ *           handle of field f — for a multicubic set, of interpn_hip_eval_cubic_grad_* ("Value and gradient of a
+ *           MULTILINEAR / MULTICUBIC handle" above hold the definitions).  The bits match, in both fma flavours, on both grid
+ *           kinds, in f64 and f32.  Both strides are in elements and >= npoints.
+ * Paths     FUSED (sets with the fused table: multilinear, N = 2 or 3): one launch of interpn::k_linear_fields_grad on that
+ *           table — the cell search, the line-group walk and the table lines of interpn::k_linear_fields; per field N + 1
+ *           reduction trees over the pieces a point's 8 lanes hold, K (N + 1) output rows stored as contiguous 64-element
+ *           runs.  No scratch, never allocates, can be captured into a graph.
+ *           PER_FIELD (multilinear N = 1, 4..8, every multicubic set, sets without the table, "fused" = 0): K calls of
+ *           interpn_hip_eval_grad_device (multicubic: interpn_hip_eval_cubic_grad_device) on the K handles with pointers into
+ *           the same blocks.
+ *           Reported with INTERPN_HIP_FIELDS_PATH_* through *path_taken and the option "last_path";
+ *           interpn_hip_fields_kernel_name says "interpn::k_linear_fields_grad<double, 3, false, true>" after a fused call.
+ * Options   "fused" (-1, 0, 1) means what it means for values.  Automatic: fused wherever the set has the table (both
+ *           paths are one-pass kernels, so the value rule's sweep clause does not apply; DESIGN.md "Field-set gradients").
+ * Checks    those of interpn_hip_fields_eval_device / _host in their order, a nearest set: INTERPN_HIP_ERR_UNSUPPORTED
+ *           (before the observation-point checks and any device work); npoints == 0: INTERPN_HIP_OK whatever the pointers
+ *           are; then out or grad NULL, out_stride or grad_stride < npoints, an obs[d] NULL: INTERPN_HIP_ERR_INVALID_ARGUMENT.
+ * Failing   a point the reference cannot evaluate fails for every field at once.  Device form: interpn_hip_fields_finish
+ * points    reports its index.  Host form: INTERPN_HIP_ERR_UNREPRESENTABLE with out[f][0..i) and grad[f][d][0..i) written
+ *           for every f, d and everything behind untouched. */
+/* Asynchronous on `stream`; `obs`, `out`, `grad`: device.  `flags`: INTERPN_HIP_EVAL_NO_ALLOC.  *path_taken (may be NULL). */
+int interpn_hip_fields_eval_grad_device(interpn_hip_fields* fields, const void* const* obs, size_t nobs, void* out,
+                                        size_t out_stride, void* grad, size_t grad_stride, size_t npoints, void* stream,
+                                        unsigned flags, int* path_taken);
+/* The same on host arrays (synchronous): chunks of at most 2 Mi points (option "host_chunk"), each chunk's coordinates cross
+ * PCIe once for all fields, the K (N + 1) result rows are copied back row by row.  nobs == ndims, obs_lens[d] == nout. */
+int interpn_hip_fields_eval_grad_host(interpn_hip_fields* fields, const void* const* obs, const size_t* obs_lens, size_t nobs,
+                                      void* out, size_t out_stride, void* grad, size_t grad_stride, size_t nout);
+
 /* Point-major field sets — the points as ONE array of shape (npoints, N), the results as ONE array of shape (npoints, K):
  * positions or ray samples in, a velocity or an RGBA per point out, without a transpose on either side.
  *

@@ -16,7 +16,8 @@ import numpy as np
 from . import _lib, one_dim, raw
 from .classes import (MulticubicRectilinear, MulticubicRegular, MultilinearRectilinear, MultilinearRegular,
                       NearestRectilinear, NearestRegular)
-from .fields import Fields, fields_lattice_plan, fields_layout, interpn_fields, interpn_fields_lattice, interpn_fields_points
+from .fields import (Fields, fields_lattice_plan, fields_layout, interpn_fields, interpn_fields_grad, interpn_fields_lattice,
+                     interpn_fields_points)
 from .handle import Interpolator, eval_device_sharded, eval_host_sharded
 
 __version__ = "0.1.0"
@@ -40,6 +41,7 @@ __all__ = [
     "raw",
     "interpn",
     "interpn_fields",
+    "interpn_fields_grad",
     "interpn_fields_lattice",
     "interpn_fields_points",
     "interpn_grad",

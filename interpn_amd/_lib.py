@@ -171,6 +171,12 @@ def load() -> ctypes.CDLL:
                                                    ctypes.c_uint, POINTER(c_int)]
     lib.interpn_hip_fields_eval_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_size_t,
                                                  c_size_t]
+    lib.interpn_hip_fields_eval_grad_device.argtypes = [c_void_p, POINTER(c_void_p), c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                                        c_size_t, c_void_p, ctypes.c_uint, POINTER(c_int)]
+    lib.interpn_hip_fields_eval_grad_device.restype = c_int
+    lib.interpn_hip_fields_eval_grad_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_size_t,
+                                                      c_void_p, c_size_t, c_size_t]
+    lib.interpn_hip_fields_eval_grad_host.restype = c_int
     lib.interpn_hip_fields_finish.argtypes = [c_void_p, c_void_p, POINTER(c_uint64)]
     lib.interpn_hip_fields_destroy.argtypes = [c_void_p]
     lib.interpn_hip_fields_destroy.restype = None

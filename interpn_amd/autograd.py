@@ -9,6 +9,9 @@ graph: the gradient with respect to `vals` is not built.
 `interp_points(it, pts)` is the same for positions kept as ONE tensor of shape `(..., N)`: its forward pass is one
 `Interpolator.eval_points_grad_tensors`, and `pts.grad` has the shape of `pts`.
 
+`interp_fields(fs, obs)` is `interp` for a field set (`Fields`): a `(K, *shape)` tensor whose forward pass is one
+`Fields.eval_grad_tensors`; the saved Jacobian turns the incoming `(K, *shape)` gradient into one gradient per coordinate.
+
 torch is imported on first use, and this module is not imported by `import interpn_amd`.
 """
 
@@ -16,6 +19,7 @@ from __future__ import annotations
 
 _FUNCTION = None
 _POINTS_FUNCTION = None
+_FIELDS_FUNCTION = None
 
 
 def _function():
@@ -89,3 +93,42 @@ def interp_points(it, pts):
     """Value of the multilinear or multicubic interpolator `it` at the points `pts`, ONE torch CUDA tensor of shape `(..., N)`
     of the handle's dtype: the result has shape `pts.shape[:-1]` and is differentiable with respect to `pts`."""
     return _points_function().apply(it, pts)
+
+
+def _fields_function():
+    """The field-set torch.autograd.Function, built on first use like `_function`."""
+    global _FIELDS_FUNCTION
+    if _FIELDS_FUNCTION is not None:
+        return _FIELDS_FUNCTION
+    import torch
+
+    class _InterpFields(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fs, *obs):
+            shape = obs[0].shape
+            flat = [o.detach().reshape(-1).contiguous() for o in obs]
+            out, jac = fs.eval_grad_tensors(flat)
+            fs.finish()
+            ctx.save_for_backward(jac)
+            ctx.obs_shape = shape
+            return out.reshape((out.shape[0],) + tuple(shape))
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            (jac,) = ctx.saved_tensors  # (K, N, n)
+            g = grad_out.reshape(jac.shape[0], -1)
+            full = (g[:, None, :] * jac).sum(0)  # grad_obs[d] = sum_f grad_out[f] * J[f, d]
+            res = [None]
+            for d in range(jac.shape[1]):
+                res.append(full[d].reshape(ctx.obs_shape) if ctx.needs_input_grad[d + 1] else None)
+            return tuple(res)
+
+    _FIELDS_FUNCTION = _InterpFields
+    return _FIELDS_FUNCTION
+
+
+def interp_fields(fs, obs):
+    """Values of the field set `fs` (a multilinear or multicubic `Fields`) at `obs` (a sequence of N equally shaped torch CUDA
+    tensors of the set's dtype): a tensor of shape `(K, *obs[0].shape)`, differentiable with respect to every tensor of `obs`.
+    The table stays a constant of the graph."""
+    return _fields_function().apply(fs, *obs)

@@ -550,6 +550,7 @@ void interpn_hip_fields_destroy(interpn_hip_fields* s) {
   if (s->stream) pool_return_kit(s->device, s->stream, s->kit_word);
   pool_free(s->device, s->host_obs);
   pool_free(s->device, s->host_out);
+  pool_free(s->device, s->host_grad);
   pool_free(s->device, s->table);
   pool_free(s->device, s->vals_owned);
   delete s;

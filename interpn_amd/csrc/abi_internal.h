@@ -12,6 +12,7 @@
 //   abi_sharded.hip   single-process multi-GPU forms
 //   abi_grad.hip      value and gradient of a multilinear or multicubic handle (eval_grad_* / eval_cubic_grad_*)
 //   abi_fields.hip    field sets: creation, column and point-major forms, options
+//   abi_fields_grad.hip  values and Jacobian of a field set (fields_eval_grad_device / _host)
 //   abi_fields_lattice.hip  field sets on a lattice (fields_eval_lattice_device / _host, fields_reserve_lattice, fields_lattice_plan)
 //   scratch_slots.h   (no HIP in it) scratch blocks between streams and stream marks: settle / take / release / reserve /
 //                     mark / the wait at destroy, against a runtime type; HipRuntime below is the product's
@@ -249,6 +250,9 @@ struct interpn_hip_fields {
   void* host_obs = nullptr;
   void* host_out = nullptr;
   size_t host_points = 0;
+  // ... and, for interpn_hip_fields_eval_grad_host, its K * N gradient rows (rows of host_grad_points elements)
+  void* host_grad = nullptr;
+  size_t host_grad_points = 0;
 };
 
 namespace interpn {

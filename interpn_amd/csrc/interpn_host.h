@@ -315,6 +315,11 @@ bool fields_geometry(size_t elem_size, int ndims, const size_t* dims, size_t nfi
 hipError_t build_fields_table(const GridDesc& g, const void* vals, size_t field_stride, int nfields, void* table, hipStream_t stream);
 hipError_t launch_linear_fields(const GridDesc& g, const void* table, int nfields, const void* const* obs, void* out,
                                 size_t out_stride, size_t npts, unsigned long long* first_bad, hipStream_t stream);
+// Values and Jacobian of a set in one pass (k_linear_fields_grad.hip, linear_fields_grad.h) on the same table: the value rows
+// as launch_linear_fields writes them, component d of field f to grad + (f * ndims + d) * grad_stride (elements).
+hipError_t launch_linear_fields_grad(const GridDesc& g, const void* table, int nfields, const void* const* obs, void* out,
+                                     size_t out_stride, void* grad, size_t grad_stride, size_t npts, unsigned long long* first_bad,
+                                     hipStream_t stream);
 // Point-major field sets (k_fields_points.hip, linear_fields_points.h): coordinate d of point i at pts[i * stride + d],
 // field f of point i to out[i * out_stride + f].  The fused kernel on the same table; and the split path's last step,
 // which turns `nfields` rows of `count` results (row f at src + f * pitch, elements) into the caller's rows.

@@ -3,7 +3,7 @@
 channels, scipy's RegularGridInterpolator with trailing value dimensions.
 
 `Fields` is the persistent form (the counterpart of `Interpolator`), `interpn_fields()` the one-call
-form (the counterpart of `interpn()`).  Row f of every result is bit-identical to what the single
+form (the counterpart of `interpn()`), `interpn_fields_grad()` the one-call form with the Jacobian.  Row f of every result is bit-identical to what the single
 interpolator of field f returns.
 """
 
@@ -53,6 +53,20 @@ def _lattice_out_stride(shape, strides, k, m, layout, contiguous) -> int:
     if shape != m + (k,):
         raise ValueError(f"out: expected shape {m + (k,)}, got {shape}")
     raise ValueError(f"out: expected a C-contiguous array, or a 2-D ({count}, >= {k}) view with contiguous rows")
+
+
+def _grad_row_stride(shape, strides) -> int:
+    """The one element stride between the K * N rows of a (K, N, n) gradient block of `shape` / `strides` (in elements; -1:
+    not a whole number of elements); ValueError for a layout the kernels cannot write."""
+    k, nd, n = (int(v) for v in shape)
+    if n == 0 or k * nd == 0:
+        return 0
+    if n > 1 and strides[2] != 1:
+        raise ValueError("grad: the last axis must be contiguous (unit stride)")
+    row = int(strides[1]) if nd > 1 else (int(strides[0]) if k > 1 else n)
+    if row < n or (k > 1 and nd > 1 and strides[0] != nd * row):
+        raise ValueError(f"grad: one uniform stride of at least {n} elements between the K * N rows (stride(0) == N * stride(1))")
+    return row
 
 
 def _is_tensor(x) -> bool:
@@ -244,6 +258,107 @@ class Fields:
         self.eval_device_ptrs([t.data_ptr() for t in obs], out.data_ptr(), max(out.stride(0), n) if n else 0, n, raw, no_alloc)
         self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
         return out
+
+    # -- values and Jacobian: (K, n) values and (K, N, n) components in one pass --------------
+    def eval_grad_host(self, obs, out=None, grad=None):
+        """Every field and its gradient at host points (synchronous; `interpn_hip_fields_eval_grad_host`): `(out, grad)`,
+        `out` of shape (K, n) with the bits of `eval_host`, `grad` of shape (K, N, n) whose block f has the bits of
+        `Interpolator.eval_grad_host` (multicubic sets: `eval_cubic_grad_host`) of field f alone.  `out`: rows contiguous,
+        any row stride >= n; `grad`: unit stride along its last axis and one uniform stride >= n between its K * N rows.
+        On "Unrepresentable coordinate value" exactly the elements in front of the failing point are written, in every
+        value and gradient row."""
+        optr, olen, nobs, _keep = _slice_of_slices("obs", obs, self.dtype)
+        n = int(olen[0]) if nobs else 0
+        k, nd, item = self.nfields, self._ndims, self.dtype.itemsize
+        if out is None:
+            out = np.zeros((k, n), dtype=self.dtype)
+        if grad is None:
+            grad = np.zeros((k, nd, n), dtype=self.dtype)
+        if not isinstance(out, np.ndarray) or out.dtype != self.dtype or out.shape != (k, n):
+            raise ValueError(f"out: expected a ({k}, {n}) array of {self.dtype.name}")
+        if not isinstance(grad, np.ndarray) or grad.dtype != self.dtype or grad.shape != (k, nd, n):
+            raise ValueError(f"grad: expected a ({k}, {nd}, {n}) array of {self.dtype.name}")
+        if n and (out.strides[1] != item or out.strides[0] % item or out.strides[0] < n * item):
+            raise ValueError("out: rows must be contiguous")
+        gstride = _grad_row_stride(grad.shape, [st // item if st % item == 0 else -1 for st in grad.strides])
+        if not (out.flags.writeable and grad.flags.writeable):
+            raise ValueError("out, grad: array is read-only")
+        vp = (c_void_p * max(nobs, 1))()
+        for i in range(nobs):
+            vp[i] = ctypes.cast(optr[i], c_void_p)
+        stride = out.strides[0] // item if n else 0
+        st = _lib.load().interpn_hip_fields_eval_grad_host(self._h, vp, olen, nobs, c_void_p(out.ctypes.data), max(stride, n),
+                                                          c_void_p(grad.ctypes.data), max(gstride, n), n)
+        self._took()
+        _lib.raise_for_status(st)
+        return out, grad
+
+    def eval_grad_device_ptrs(self, obs_ptrs, out_ptr: int, out_stride: int, grad_ptr: int, grad_stride: int, npoints: int,
+                              stream: int = 0, no_alloc: bool = False) -> str:
+        """Enqueue one value-and-Jacobian evaluation on device buffers given as raw addresses; returns the path taken."""
+        n = len(obs_ptrs)
+        vp = (c_void_p * max(n, 1))()
+        for i, p in enumerate(obs_ptrs):
+            vp[i] = c_void_p(int(p))
+        path = ctypes.c_int(0)
+        st = _lib.load().interpn_hip_fields_eval_grad_device(self._h, vp, n, c_void_p(int(out_ptr)), int(out_stride),
+                                                            c_void_p(int(grad_ptr)), int(grad_stride), int(npoints),
+                                                            c_void_p(int(stream)), _lib.EVAL_NO_ALLOC if no_alloc else 0,
+                                                            ctypes.byref(path))
+        _lib.raise_for_status(st)
+        self.last_path = "fused" if path.value == _lib.FIELDS_PATH_FUSED else "per_field"
+        self._pending_streams.setdefault(int(stream), None)
+        return self.last_path
+
+    def eval_grad_tensors(self, obs, out=None, grad=None, stream=None, no_alloc: bool = False):
+        """The same on torch CUDA tensors (asynchronous on torch's current stream unless given;
+        `interpn_hip_fields_eval_grad_device`): `(out, grad)` of shapes (K, n) and (K, N, n).  Sets with the fused table
+        run one launch of `interpn::k_linear_fields_grad`, which allocates nothing and can be captured into a graph;
+        `last_path` says which path ran.  `out`: rows contiguous, any row stride >= n; `grad`: unit stride along its last
+        axis and one uniform stride >= n between its K * N rows.  Call `finish()` to synchronise and surface
+        "Unrepresentable coordinate value"."""
+        import torch
+
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        obs = list(obs)
+        dev = self.device()
+        for i, t in enumerate(obs):
+            if not (t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
+                raise TypeError(f"obs[{i}]: expected a contiguous 1-D {want} CUDA tensor")
+            if t.device.index not in (None, dev):
+                raise ValueError(f"obs[{i}] is on {t.device} but this set lives on cuda:{dev}")
+        n = obs[0].numel() if obs else 0
+        for t in obs:
+            if t.numel() != n:
+                raise AssertionError("Dimension mismatch")
+        k, nd = self.nfields, self._ndims
+        where = torch.device("cuda", dev)
+        if out is None:
+            out = torch.empty((k, n), dtype=want, device=where)
+        elif not (out.is_cuda and out.dim() == 2 and out.dtype == want and tuple(out.shape) == (k, n)):
+            raise TypeError(f"out: expected a ({k}, {n}) {want} CUDA tensor")
+        elif n and (out.stride(1) != 1 or out.stride(0) < n):
+            raise ValueError("out: rows must be contiguous")
+        if grad is None:
+            grad = torch.empty((k, nd, n), dtype=want, device=where)
+        elif not (grad.is_cuda and grad.dim() == 3 and grad.dtype == want and tuple(grad.shape) == (k, nd, n)):
+            raise TypeError(f"grad: expected a ({k}, {nd}, {n}) {want} CUDA tensor")
+        gstride = _grad_row_stride(tuple(grad.shape), grad.stride())
+        owner = torch.cuda.current_stream(dev) if stream is None else stream
+        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        self.eval_grad_device_ptrs([t.data_ptr() for t in obs], out.data_ptr(), max(out.stride(0), n) if n else 0, grad.data_ptr(),
+                                   max(gstride, n) if n else 0, n, raw, no_alloc)
+        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        return out, grad
+
+    def eval_grad(self, obs, out=None, grad=None, **kwargs):
+        """`eval_grad_tensors` for torch tensors, `eval_grad_host` for numpy arrays (by the type of `obs[0]`)."""
+        obs = list(obs)
+        if obs and _is_tensor(obs[0]):
+            return self.eval_grad_tensors(obs, out, grad, **kwargs)
+        if kwargs:
+            raise TypeError(f"eval_grad on host arrays takes no {sorted(kwargs)}")
+        return self.eval_grad_host(obs, out, grad)
 
     # -- point-major evaluation: (n, N) points in, (n, K) values out -------------------------
     def reserve_points(self, npoints: int, nstreams: int = 1) -> None:
@@ -682,6 +797,75 @@ def interpn_fields(obs, grids, vals, *, method="linear", field_axis: int = 0, ou
             out[...] = res
         return out
     return res.contiguous() if on_device else np.ascontiguousarray(res)
+
+
+def interpn_fields_grad(obs, grids, vals, *, method="linear", field_axis: int = 0, linearize_extrapolation: bool = True,
+                        assume_regular: bool = False):
+    """`interpn_fields()` with the Jacobian: every field and its derivative with respect to every coordinate at the
+    observation points, one pass over the points where the set has the fused kernel (`Fields.eval_grad`).  The rules are
+    those of `interpn_fields` (ravelled inputs, dtype from `vals`, exact-spacing regularity test, host arrays or torch CUDA
+    tensors as points); `method` is "linear" or "cubic" ("nearest" has no gradient: the library's "unsupported" error).
+
+    Returns `(out, jac)`.  `vals` (K, *dims): `out` (K, *obs[0].shape), `jac` (K, N, *obs[0].shape), `jac[f, d]` the
+    derivative of field f with respect to coordinate d, with the bits of `interpn_grad` of field f.  With `field_axis=-1`
+    the scipy layout: `vals` (*dims, K), `out` (*obs[0].shape, K), `jac` (*obs[0].shape, K, N) — permuted copies made here,
+    not by the kernel."""
+    from . import _check_regular, _is_cuda_tensor
+
+    if field_axis not in (0, -1):
+        raise ValueError("field_axis: expected 0 (fields first) or -1 (fields last)")
+    if method not in ("linear", "cubic", "nearest"):
+        raise ValueError(f"Unsupported interpolation configuration: {method}")
+    if not (isinstance(vals, np.ndarray) or _is_tensor(vals)):
+        raise TypeError("vals: expected a numpy array or a torch tensor with a field axis")
+    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
+    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
+    if len(vals.shape) < 2:
+        raise ValueError("vals: expected a field axis besides the grid's values")
+    grids = [np.ascontiguousarray(np.asarray(g).ravel()).astype(dtype, copy=False) for g in grids]
+    nper = int(np.prod([g.size for g in grids], dtype=object))
+    k = int(vals.shape[field_axis])
+    if k * nper != int(np.prod(tuple(vals.shape), dtype=object)):
+        raise ValueError(f"vals: expected {k} x {nper} values for grids of {[g.size for g in grids]}, got shape {tuple(vals.shape)}")
+    if field_axis == -1:  # (*dims, K) -> (K, prod(dims))
+        vals = vals.reshape(nper, k).T
+    vals = (vals.contiguous() if _is_tensor(vals) else np.ascontiguousarray(vals)).reshape(k, nper)
+    on_device = bool(len(obs)) and _is_cuda_tensor(obs[0])
+    pshape = tuple(obs[0].shape) if len(obs) else (0,)
+    nd = len(grids)
+    device = -1
+    if on_device:
+        import torch
+
+        device = obs[0].device.index if obs[0].device.index is not None else torch.cuda.current_device()
+        obs_flat = [x.reshape(-1).contiguous() for x in obs]
+    else:
+        if _is_tensor(vals):
+            vals = vals.cpu().numpy()
+        obs_flat = [np.ascontiguousarray(np.asarray(x).ravel()) for x in obs]
+    if assume_regular or _check_regular(grids):
+        starts = np.array([g[0] for g in grids], dtype=dtype)
+        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
+        fs = Fields.regular(method, [g.size for g in grids], starts, steps, vals, linearize_extrapolation=linearize_extrapolation,
+                            device=device, dtype=dtype)
+    else:
+        fs = Fields.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
+    try:
+        if on_device:
+            out, jac = fs.eval_grad_tensors(obs_flat)
+            fs.finish()
+        else:
+            out, jac = fs.eval_grad_host(obs_flat)
+    finally:
+        fs.close()
+    out = out.reshape((k,) + pshape)
+    jac = jac.reshape((k, nd) + pshape)
+    if field_axis == 0:
+        return out, jac
+    np_ = len(pshape)
+    if on_device:
+        return (out.permute(*range(1, np_ + 1), 0).contiguous(), jac.permute(*range(2, np_ + 2), 0, 1).contiguous())
+    return (np.ascontiguousarray(np.moveaxis(out, 0, -1)), np.ascontiguousarray(np.moveaxis(np.moveaxis(jac, 0, -1), 0, -1)))
 
 
 def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, linearize_extrapolation: bool = True,
