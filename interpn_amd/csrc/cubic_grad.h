@@ -58,13 +58,14 @@ __device__ __forceinline__ void cubic_regular_node_vd(T v0, T v1, T v2, T v3, co
   T k0 = cd / two;
   k0 = low ? -k0 : k0;
   T k1n = (v3 - v1) / two;
+  // multicubic/regular.rs:528, :549, :583, :605 and multicubic/regular_recursive.rs:519, :570, :592
   T k1e = mul_add<FMA>(two, dy, -k0);
   if constexpr (ARMS && FMA) {
-    if (d.k1_plain) k1e = two * dy - k0;
+    if (d.k1_plain) k1e = two * dy - k0;  // multicubic/regular_recursive.rs:536
   }
   T k1 = (low || high) ? k1e : k1n;
   if (d.linear) {
-    val = mul_add<FMA>(k1, d.tt - one, ya);
+    val = mul_add<FMA>(k1, d.tt - one, ya);  // multicubic/regular.rs:560, :616, multicubic/regular_recursive.rs:547, :603
     der = k1;
     return;
   }
@@ -73,8 +74,8 @@ __device__ __forceinline__ void cubic_regular_node_vd(T v0, T v1, T v2, T v3, co
   der = hermite_deriv<FMA, T>(d.tt, c.c1, c.c2, c.c3);
 }
 
-// The same on a rectilinear grid: cubic_rect_node's operations.
-template <bool FMA, typename T>
+// The same on a rectilinear grid: cubic_rect_node's operations (ARMS: that function's; the derivative node uses the same k1).
+template <bool FMA, typename T, bool ARMS = false>
 __device__ __forceinline__ void cubic_rect_node_vd(T v0, T v1, T v2, T v3, const CubicDimRect<T>& d, T& val, T& der) {
   const T two = (T)2, one = (T)1;
   T y0, y1, dy, k0, k1;
@@ -86,13 +87,16 @@ __device__ __forceinline__ void cubic_rect_node_vd(T v0, T v1, T v2, T v3, const
     k1 = cd_unit_a<FMA>(v1, v2, v3, d.r1, d.a1, d.c1);
   } else {
     cubic_rect_saturated<FMA, T>(v0, v1, v2, v3, d, y0, y1, dy, k0);
-    k1 = two * dy - k0;
+    k1 = two * dy - k0;  // multicubic/rectilinear.rs:471, :493, :515, :532 and multicubic/rectilinear_recursive.rs:469, :519: never fused
+    if constexpr (ARMS && FMA) {
+      if (d.fma_linear & kRectFuseK1) k1 = dev_fma<T>(two, dy, -k0);  // multicubic/rectilinear_recursive.rs:447, :502
+    }
     if (d.linear) {
-      if (FMA && d.fma_linear) {
+      if (FMA && d.fma_linear) {  // multicubic/rectilinear_recursive.rs:482, :532
         val = dev_fma<T>(k1, d.t - one, y1);
       } else {
         T p = k1 * (d.t - one);
-        val = y1 + p;
+        val = y1 + p;  // multicubic/rectilinear.rs:500, :539
       }
       der = k1;
       return;
@@ -219,7 +223,7 @@ __device__ __attribute__((noinline)) T cubic_grad_rect_node_ool(T v0, T v1, T v2
   dr.sat = sat; dr.linear = linear; dr.fma_linear = fma_linear; dr.t = t;
   dr.r0 = r0; dr.a0 = a0; dr.c0 = c0; dr.r1 = r1; dr.a1 = a1; dr.c1 = c1;
   T val, der;
-  cubic_rect_node_vd<FMA, T>(v0, v1, v2, v3, dr, val, der);
+  cubic_rect_node_vd<FMA, T, true>(v0, v1, v2, v3, dr, val, der);
   return deriv ? der : val;
 }
 
@@ -228,7 +232,7 @@ __global__ void __launch_bounds__(kBlock) k_cubic_grad_n(const CubicGradGenericA
   const int N = a.ndims;
   const size_t nthreads = (size_t)gridDim.x * kBlock;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < a.npts; i += nthreads) {
-    int c_sat[kMaxDims], c_lin[kMaxDims], c_plain[kMaxDims];
+    int c_sat[kMaxDims], c_lin[kMaxDims], c_plain[kMaxDims];  // c_plain: k1_plain (regular), CubicDimRect::fma_linear (rectilinear)
     T c_t[kMaxDims], c_w[kMaxDims];
     T rc_r0[kMaxDims], rc_a0[kMaxDims], rc_c0[kMaxDims], rc_r1[kMaxDims], rc_a1[kMaxDims], rc_c1[kMaxDims];
     unsigned long long base = 0;
@@ -253,7 +257,7 @@ __global__ void __launch_bounds__(kBlock) k_cubic_grad_n(const CubicGradGenericA
         ax.g = a.grid[d]; ax.tab = nullptr; ax.n = a.n[d]; ax.M = 0; ax.g0 = (T)0; ax.scale = (T)0;
         CubicDimRect<T> dr;
         loc = cubic_rect_locate<T>(ax, x, a.linearize, a.fma_linear != 0, dr);
-        c_sat[d] = dr.sat; c_lin[d] = dr.linear; c_plain[d] = 0; c_t[d] = dr.t;
+        c_sat[d] = dr.sat; c_lin[d] = dr.linear; c_plain[d] = dr.fma_linear; c_t[d] = dr.t;
         rc_r0[d] = dr.r0; rc_a0[d] = dr.a0; rc_c0[d] = dr.c0;
         rc_r1[d] = dr.r1; rc_a1[d] = dr.a1; rc_c1[d] = dr.c1;
         c_w[d] = cubic_rect_width<T>(a.grid[d], loc, dr.sat);
@@ -266,7 +270,7 @@ __global__ void __launch_bounds__(kBlock) k_cubic_grad_n(const CubicGradGenericA
       if constexpr (KIND == kRegular)
         return cubic_grad_regular_node_ool<FMA, T>(v[0], v[1], v[2], v[3], c_sat[d], c_lin[d], c_plain[d], c_t[d], deriv);
       else
-        return cubic_grad_rect_node_ool<FMA, T>(v[0], v[1], v[2], v[3], c_sat[d], c_lin[d], a.fma_linear, c_t[d], rc_r0[d],
+        return cubic_grad_rect_node_ool<FMA, T>(v[0], v[1], v[2], v[3], c_sat[d], c_lin[d], c_plain[d], c_t[d], rc_r0[d],
                                                 rc_a0[d], rc_c0[d], rc_r1[d], rc_a1[d], rc_c1[d], deriv);
     };
 

@@ -487,7 +487,7 @@ struct LinearTree {
     for (int i = 0; i < 2; ++i) {
       T y0 = a.v[i];
       T dy = b.v[i] - y0;
-      r.v[i] = mul_add<FMA>(t[D - 1], dy, y0);  // regular.rs:378-385
+      r.v[i] = mul_add<FMA>(t[D - 1], dy, y0);  // multilinear/regular.rs:385, multilinear/rectilinear.rs:321
     }
     return r;
   }
@@ -529,7 +529,7 @@ __device__ __forceinline__ HermiteCoef<T> hermite_coef(T y0, T dy, T k0, T k1) {
 template <bool FMA, typename T>
 __device__ __forceinline__ T hermite_eval(T t, T y0, T c1, T c2, T c3) {
   if constexpr (FMA) {
-    return dev_fma<T>(dev_fma<T>(dev_fma<T>(c3, t, c2), t, c1), t, y0);
+    return dev_fma<T>(dev_fma<T>(dev_fma<T>(c3, t, c2), t, c1), t, y0);  // multicubic/mod.rs:89
   } else {
     T i0 = t * c3;
     T i1 = c2 + i0;
@@ -634,14 +634,16 @@ __device__ __forceinline__ T cubic_regular_node(T v0, T v1, T v2, T v3, const Cu
   T k0 = cd / two;
   k0 = low ? -k0 : k0;
   T k1n = (v3 - v1) / two;
-  T k1e = mul_add<FMA>(two, dy, -k0);  // regular.rs:525-528: fused under the `fma` feature (the same bits unless 2 dy overflows)
+  // fused under the `fma` feature (the same bits unless 2 dy overflows): multicubic/regular.rs:528, :549, :583, :605 and
+  // multicubic/regular_recursive.rs:519, :570, :592
+  T k1e = mul_add<FMA>(two, dy, -k0);
   if constexpr (ARMS && FMA) {
-    if (d.k1_plain) k1e = two * dy - k0;
+    if (d.k1_plain) k1e = two * dy - k0;  // multicubic/regular_recursive.rs:536
   }
   T k1 = (low || high) ? k1e : k1n;
   if (d.linear) {
     T y1 = ya;  // vals[0] (low) / vals[3] (high)
-    return mul_add<FMA>(k1, d.tt - one, y1);  // regular.rs:553-561, :609-617
+    return mul_add<FMA>(k1, d.tt - one, y1);  // multicubic/regular.rs:560, :616, multicubic/regular_recursive.rs:547, :603
   }
   return hermite<FMA>(d.tt, y0, dy, k0, k1);
 }
@@ -651,11 +653,19 @@ __device__ __forceinline__ T cubic_regular_node(T v0, T v1, T v2, T v3, const Cu
 // depends only on the dimension (spacings, spacing ratios, weights a and c of the
 // non-uniform central difference, t) is computed once per point and dimension; the
 // per-node part is the value-dependent remainder, evaluated in the reference's order.
+enum RectFuse : int { kRectFuseLinear = 1, kRectFuseK1 = 2 };
+
 template <typename T>
 struct CubicDimRect {
   int sat;
   int linear;      // OutsideLow/OutsideHigh with linearize_extrapolation
-  int fma_linear;  // recursive arm fuses the linearized branch (rectilinear_recursive.rs:467,527)
+  // What the reference's recursive arm (N >= 5) fuses under `fma` and its flattened arm does not; 0 in every flattened-arm kernel.
+  //   kRectFuseLinear  the linearized branch (multicubic/rectilinear_recursive.rs:482, :532 against multicubic/rectilinear.rs:500, :539)
+  //   kRectFuseK1      this point's k1 = 2 dy - k0: InsideLow and InsideHigh only (multicubic/rectilinear_recursive.rs:447, :502; not
+  //                    :469, :519, and no class of the flattened arm: multicubic/rectilinear.rs:471, :493, :515, :532).  2 dy is exact,
+  //                    so the forms differ only where 2 dy overflows.  Set by cubic_rect_locate, which knows inside from outside;
+  //                    read by cubic_rect_node<FMA, T, true> and cubic_rect_node_vd<FMA, T, true> alone (the runtime-N kernels).
+  int fma_linear;
   T t;
   // cd(y0,y1,y2,hA,hB) = a*b + c*d, a = hA/(hA+hB), b = (y2-y1)/hB, c = hB/(hB+hA), d = (y1-y0)/hA
   //   None: k0 = cd(v0,v1,v2, h01/h12, 1),  k1 = cd(v1,v2,v3, 1, h23/h12)
@@ -718,7 +728,7 @@ __device__ __forceinline__ T cd_unit_b(T y0, T y1, T y2, T r, T a, T c) {
   T b = y2 - y1;
   T dd = (y1 - y0) / r;
   if constexpr (FMA) {
-    return dev_fma<T>(a, b, c * dd);
+    return dev_fma<T>(a, b, c * dd);  // multicubic/mod.rs:115
   } else {
     T ab = a * b;
     T cdd = c * dd;
@@ -731,7 +741,7 @@ __device__ __forceinline__ T cd_unit_a(T y0, T y1, T y2, T r, T a, T c) {
   T b = (y2 - y1) / r;
   T dd = y1 - y0;
   if constexpr (FMA) {
-    return dev_fma<T>(a, b, c * dd);
+    return dev_fma<T>(a, b, c * dd);  // multicubic/mod.rs:115
   } else {
     T ab = a * b;
     T cdd = c * dd;
@@ -764,7 +774,7 @@ __device__ __forceinline__ void cubic_rect_saturated(T v0, T v1, T v2, T v3, con
   dy = low ? v0 - v1 : up;
 }
 
-template <bool FMA, typename T>
+template <bool FMA, typename T, bool ARMS = false>
 __device__ __forceinline__ T cubic_rect_node(T v0, T v1, T v2, T v3, const CubicDimRect<T>& d) {
   const T two = (T)2, one = (T)1;
   if (d.sat == kSatNone) {
@@ -776,11 +786,14 @@ __device__ __forceinline__ T cubic_rect_node(T v0, T v1, T v2, T v3, const Cubic
   }
   T y0, y1, dy, k0;
   cubic_rect_saturated<FMA, T>(v0, v1, v2, v3, d, y0, y1, dy, k0);
-  T k1 = two * dy - k0;
+  T k1 = two * dy - k0;  // multicubic/rectilinear.rs:471, :493, :515, :532 and multicubic/rectilinear_recursive.rs:469, :519: never fused
+  if constexpr (ARMS && FMA) {
+    if (d.fma_linear & kRectFuseK1) k1 = dev_fma<T>(two, dy, -k0);  // multicubic/rectilinear_recursive.rs:447, :502 (the same bits unless 2 dy overflows)
+  }
   if (d.linear) {
-    if (FMA && d.fma_linear) return dev_fma<T>(k1, d.t - one, y1);
+    if (FMA && d.fma_linear) return dev_fma<T>(k1, d.t - one, y1);  // multicubic/rectilinear_recursive.rs:482, :532
     T p = k1 * (d.t - one);
-    return y1 + p;  // rectilinear.rs:500,:539 — never fused in the flattened arm
+    return y1 + p;  // multicubic/rectilinear.rs:500, :539 — never fused in the flattened arm
   }
   return hermite<FMA>(d.t, y0, dy, k0, k1);
 }

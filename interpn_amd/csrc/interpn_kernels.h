@@ -125,7 +125,7 @@ __global__ void __launch_bounds__(kBlock) k_linear_regular(const RegularArgs<T, 
         T floc;
         ok &= regular_floc<T>(x[u][d], a.start[d], a.step[d], &floc);  // regular.rs:415-418
         const int loc = clamp_loc<T>(floc, a.n[d] - 2);                // regular.rs:420-422
-        // regular.rs:334-339: fused in the flattened arm when the `fma` feature is on
+        // multilinear/regular.rs:337 (regular.rs:334-339): fused in the flattened arm when the `fma` feature is on
         const T index_zero_loc = mul_add<FMA>(a.step[d], (T)loc, a.start[d]);
         t[u][d] = (x[u][d] - index_zero_loc) / a.step[d];
         base[u] += (unsigned)loc * a.stride[d];
@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(kBlock) k_linear_regular(const RegularArgs<T, 
       Leaf<T, 2> r = LinearTree<T, unsigned, N - 1, FMA>::run(a.vals, base[u], a.stride, t[u]);
       const T y0 = r.v[0];
       const T dy = r.v[1] - y0;
-      const T res = mul_add<FMA>(t[u][N - 1], dy, y0);  // regular.rs:396-402
+      const T res = mul_add<FMA>(t[u][N - 1], dy, y0);  // multilinear/regular.rs:402 (regular.rs:396-402)
       if (i < a.npts) stream_store(a.out + i, res);
     }
   }
@@ -179,7 +179,7 @@ __device__ __forceinline__ void linear_rectilinear_body(const RectArgs<T, N>& a,
       Leaf<T, 2> r = LinearTree<T, unsigned, N - 1, FMA>::run(a.vals, base[u], a.stride, t[u]);
       const T y0 = r.v[0];
       const T dy = r.v[1] - y0;
-      const T res = mul_add<FMA>(t[u][N - 1], dy, y0);  // rectilinear.rs:339-344
+      const T res = mul_add<FMA>(t[u][N - 1], dy, y0);  // multilinear/rectilinear.rs:344 (rectilinear.rs:339-344)
       if (i < a.npts) stream_store(a.out + i, res);
     }
   }
@@ -248,7 +248,8 @@ __device__ __forceinline__ int cubic_rect_locate(const Axis<T>& ax, T x, int lin
   else if (iloc == n - 3) { d.sat = kSatHigh; }
   else { d.sat = kSatNone; }
   d.linear = (outside && linearize) ? 1 : 0;
-  d.fma_linear = fma_linear ? 1 : 0;
+  // the recursive arm: the linearized branch, and k1 of InsideLow / InsideHigh (multicubic/rectilinear_recursive.rs:447, :502)
+  d.fma_linear = fma_linear ? (kRectFuseLinear | ((d.sat != kSatNone && !outside) ? kRectFuseK1 : 0)) : 0;
   cubic_rect_dim_setup<T, RECIP>(g, loc, x, d);
   return loc;
 }
@@ -338,7 +339,9 @@ struct GenericArgs {
   unsigned long long stride[kMaxDims];
   int linearize;
   int fma_index;   // linear regular: index_zero_loc fused (flattened arm, N <= 6)
-  int fma_linear;  // the reference's recursive arm (N >= 5): cubic rectilinear's linearized branch is fused; cubic regular's OutsideLow k1 is not
+  // the reference's recursive arm (N >= 5): cubic rectilinear's linearized branch and its InsideLow / InsideHigh k1 are fused;
+  // cubic regular's OutsideLow k1 is not
+  int fma_linear;
 };
 
 // Out-of-line node evaluators for the runtime-N kernel (keeps its code size bounded).
@@ -348,7 +351,7 @@ __device__ __attribute__((noinline)) T cubic_rect_node_ool(T v0, T v1, T v2, T v
   CubicDimRect<T> dr;
   dr.sat = sat; dr.linear = linear; dr.fma_linear = fma_linear; dr.t = t;
   dr.r0 = r0; dr.a0 = a0; dr.c0 = c0; dr.r1 = r1; dr.a1 = a1; dr.c1 = c1;
-  return cubic_rect_node<FMA, T>(v0, v1, v2, v3, dr);
+  return cubic_rect_node<FMA, T, true>(v0, v1, v2, v3, dr);
 }
 
 template <typename T, int METHOD, int KIND, bool FMA>
@@ -361,7 +364,7 @@ __global__ void __launch_bounds__(kBlock) k_generic(const GenericArgs<T> a) {
     T tlin[kMaxDims];
     CubicDimRegular<T> dreg[kMaxDims];
     // per-dimension state of the rectilinear cubic node, kept as separate arrays (runtime-indexed)
-    int rc_sat[kMaxDims], rc_lin[kMaxDims];
+    int rc_sat[kMaxDims], rc_lin[kMaxDims], rc_fuse[kMaxDims];
     T rc_t[kMaxDims], rc_r0[kMaxDims], rc_a0[kMaxDims], rc_c0[kMaxDims], rc_r1[kMaxDims], rc_a1[kMaxDims], rc_c1[kMaxDims];
     unsigned long long base = 0;
     bool ok = true;
@@ -374,6 +377,7 @@ __global__ void __launch_bounds__(kBlock) k_generic(const GenericArgs<T> a) {
         if constexpr (METHOD == kCubic) ok &= floc != (T)-9223372036854775808.0;
         if constexpr (METHOD == kLinear) {
           loc = clamp_loc<T>(floc, a.n[d] - 2);
+          // multilinear/regular.rs:337: the flattened arm's index_zero_loc is fused, the recursive arm's is not
           const T izl = (FMA && a.fma_index) ? dev_fma<T>(a.step[d], (T)loc, a.start[d])
                                              : mul_add<false>(a.step[d], (T)loc, a.start[d]);
           tlin[d] = (x - izl) / a.step[d];
@@ -401,7 +405,7 @@ __global__ void __launch_bounds__(kBlock) k_generic(const GenericArgs<T> a) {
           ax.g = g; ax.tab = nullptr; ax.n = a.n[d]; ax.M = 0; ax.g0 = (T)0; ax.scale = (T)0;
           CubicDimRect<T> dr;
           loc = cubic_rect_locate<T>(ax, x, a.linearize, a.fma_linear != 0, dr);
-          rc_sat[d] = dr.sat; rc_lin[d] = dr.linear; rc_t[d] = dr.t;
+          rc_sat[d] = dr.sat; rc_lin[d] = dr.linear; rc_fuse[d] = dr.fma_linear; rc_t[d] = dr.t;
           rc_r0[d] = dr.r0; rc_a0[d] = dr.a0; rc_c0[d] = dr.c0;
           rc_r1[d] = dr.r1; rc_a1[d] = dr.a1; rc_c1[d] = dr.c1;
         }
@@ -414,11 +418,11 @@ __global__ void __launch_bounds__(kBlock) k_generic(const GenericArgs<T> a) {
       if constexpr (METHOD == kLinear) {
         const T y0 = v[0];
         const T dy = v[1] - y0;
-        return mul_add<FMA>(tlin[d], dy, y0);
+        return mul_add<FMA>(tlin[d], dy, y0);  // multilinear/regular_recursive.rs:384, multilinear/rectilinear_recursive.rs:331
       } else if constexpr (KIND == kRegular) {
         return cubic_regular_node<FMA, T, true>(v[0], v[1], v[2], v[3], dreg[d]);
       } else {
-        return cubic_rect_node_ool<FMA, T>(v[0], v[1], v[2], v[3], rc_sat[d], rc_lin[d], a.fma_linear, rc_t[d],
+        return cubic_rect_node_ool<FMA, T>(v[0], v[1], v[2], v[3], rc_sat[d], rc_lin[d], rc_fuse[d], rc_t[d],
                                            rc_r0[d], rc_a0[d], rc_c0[d], rc_r1[d], rc_a1[d], rc_c1[d]);
       }
     };
@@ -471,6 +475,7 @@ __global__ void __launch_bounds__(kBlock) k_generic_n(const GenericArgs<T> a) {
         if constexpr (METHOD == kCubic) ok &= floc != (T)-9223372036854775808.0;
         if constexpr (METHOD == kLinear) {
           loc = clamp_loc<T>(floc, a.n[d] - 2);
+          // multilinear/regular.rs:337: the flattened arm's index_zero_loc is fused, the recursive arm's is not
           const T izl = (FMA && a.fma_index) ? dev_fma<T>(a.step[d], (T)loc, a.start[d])
                                              : mul_add<false>(a.step[d], (T)loc, a.start[d]);
           tlin[d] = (x - izl) / a.step[d];
@@ -504,9 +509,10 @@ __global__ void __launch_bounds__(kBlock) k_generic_n(const GenericArgs<T> a) {
     if (!ok) atomicMin(a.first_bad, (unsigned long long)i);
 
     auto node = [&](T v0, T v1, T v2, T v3, int j) -> T {
+      // multilinear/regular_recursive.rs:384, multilinear/rectilinear_recursive.rs:331
       if constexpr (METHOD == kLinear) return mul_add<FMA>(tlin[j], v1 - v0, v0);
       else if constexpr (KIND == kRegular) return cubic_regular_node<FMA, T, true>(v0, v1, v2, v3, dreg[j]);
-      else return cubic_rect_node<FMA, T>(v0, v1, v2, v3, drect[j]);
+      else return cubic_rect_node<FMA, T, true>(v0, v1, v2, v3, drect[j]);
     };
     T result;
     const T* row0 = a.vals + base;

@@ -35,7 +35,9 @@ static hipError_t launch_mk(const GridDesc& g, const T* const* obs, T* out, size
   a.linearize = g.linearize;
   // FMA sites that differ between the reference's flattened and recursive arms:
   a.fma_index = g.ndims <= 6;   // multilinear/regular.rs:337 vs regular_recursive.rs:310-313
-  a.fma_linear = g.ndims >= 5;  // multicubic/rectilinear.rs:500,539 vs rectilinear_recursive.rs:467,527
+  // multicubic/rectilinear.rs:500, :539 vs multicubic/rectilinear_recursive.rs:482, :532 (the linearized branch), and k1 of
+  // InsideLow / InsideHigh: multicubic/rectilinear.rs:471, :515 vs multicubic/rectilinear_recursive.rs:447, :502
+  a.fma_linear = g.ndims >= 5;
   unsigned long long acc = 1;
   for (int d = kMaxDims - 1; d >= 0; --d) {
     if (d < g.ndims) {

@@ -88,7 +88,7 @@ __device__ __forceinline__ void nearest_body(const NearestArgs<T, N>& a, const u
           T floc;
           ok &= regular_floc<T>(x, a.start[d], a.step[d], &floc);  // nearest/regular.rs:306-309
           loc = clamp_loc<T>(floc, a.n[d] - 2);
-          const T izl = mul_add<FMA>(a.step[d], (T)loc, a.start[d]);  // regular.rs:272-275
+          const T izl = mul_add<FMA>(a.step[d], (T)loc, a.start[d]);  // nearest/regular.rs:275
           dt = (x - izl) / a.step[d];
         }
         const int offset = (dt <= half) ? 0 : 1;  // regular.rs:283-287 (NaN compares false => 1)

@@ -98,7 +98,7 @@ inline T normalized_hermite_spline(T t, T y0, T dy, T k0, T k1) {
   T c2 = b - (a + a);
   T c3 = a - b;
   if (FMA) {
-    return std::fma(std::fma(std::fma(c3, t, c2), t, c1), t, y0);  // mod.rs:89
+    return std::fma(std::fma(std::fma(c3, t, c2), t, c1), t, y0);  // multicubic/mod.rs:89
   } else {
     T i0 = t * c3;
     T i1 = c2 + i0;
@@ -117,7 +117,7 @@ inline T centered_difference_nonuniform(T y0, T y1, T y2, T h01, T h12) {
   T c = h12 / (h12 + h01);
   T d = (y1 - y0) / h01;
   if (FMA) {
-    return std::fma(a, b, c * d);  // mod.rs:115
+    return std::fma(a, b, c * d);  // multicubic/mod.rs:115
   } else {
     T ab = a * b;
     T cd = c * d;
@@ -148,8 +148,10 @@ inline T cubic_regular_inner(const T* vals, T t, Sat sat, bool linearize, bool r
       T y1 = vals[0];
       T dy = vals[0] - vals[1];
       T k0 = -(vals[2] - vals[0]) / two;
+      // fused: multicubic/regular.rs:528, :549 and multicubic/regular_recursive.rs:519; the recursive arm's OutsideLow is not:
+      // multicubic/regular_recursive.rs:536
       T k1 = (recursive_arm && sat == OutsideLow) ? two * dy - k0 : mul_add<FMA>(two, dy, -k0);
-      if (sat == OutsideLow && linearize) return mul_add<FMA>(k1, tt - one, y1);  // regular.rs:553-561
+      if (sat == OutsideLow && linearize) return mul_add<FMA>(k1, tt - one, y1);  // multicubic/regular.rs:560, multicubic/regular_recursive.rs:547
       return normalized_hermite_spline<FMA>(tt, y0, dy, k0, k1);
     }
     case InsideHigh:
@@ -159,19 +161,23 @@ inline T cubic_regular_inner(const T* vals, T t, Sat sat, bool linearize, bool r
       T y1 = vals[3];
       T dy = vals[3] - vals[2];
       T k0 = (vals[3] - vals[1]) / two;
-      T k1 = mul_add<FMA>(two, dy, -k0);
-      if (sat == OutsideHigh && linearize) return mul_add<FMA>(k1, tt - one, y1);  // regular.rs:609-617
+      T k1 = mul_add<FMA>(two, dy, -k0);  // multicubic/regular.rs:583, :605, multicubic/regular_recursive.rs:570, :592
+      if (sat == OutsideHigh && linearize) return mul_add<FMA>(k1, tt - one, y1);  // multicubic/regular.rs:616, multicubic/regular_recursive.rs:603
       return normalized_hermite_spline<FMA>(tt, y0, dy, k0, k1);
     }
   }
   return (T)0;
 }
 
-// src/multicubic/rectilinear.rs:413-545 (flattened: linearized branch is NEVER fused,
-// :500,:539) and rectilinear_recursive.rs:385-545 (recursive: fused under `fma`, :467,:527).
+// src/multicubic/rectilinear.rs:413-545 (flattened: the linearized branch is NEVER fused, multicubic/rectilinear.rs:500, :539,
+// and neither is k1 = 2 dy - k0 of any saturated class, multicubic/rectilinear.rs:471, :493, :515, :532) and
+// rectilinear_recursive.rs:385-545 (`recursive_arm`, N >= 5: under `fma` the linearized branch is fused,
+// multicubic/rectilinear_recursive.rs:482, :532, and so is k1 of InsideLow and InsideHigh, multicubic/rectilinear_recursive.rs:447, :502,
+// while k1 of OutsideLow and OutsideHigh is not, :469, :519).  2 dy is exact, so the two forms of k1 differ only where 2 dy
+// overflows.
 template <bool FMA, typename T>
 inline T cubic_rectilinear_inner(const T* vals, const T* g, T x, Sat sat, bool linearize,
-                                 bool fma_linearize) {
+                                 bool recursive_arm) {
   const T one = (T)1, two = (T)2;
   switch (sat) {
     case SatNone: {
@@ -193,12 +199,13 @@ inline T cubic_rectilinear_inner(const T* vals, const T* g, T x, Sat sat, bool l
       T h01 = g[1] - g[0];
       T h12 = g[2] - g[1];
       T k0 = -centered_difference_nonuniform<FMA>(vals[0], vals[1], vals[2], one, h12 / h01);
-      T k1 = two * dy - k0;  // rectilinear.rs:471,493,515,532: never fused, with or without the `fma` feature
+      T k1 = (recursive_arm && sat == InsideLow) ? mul_add<FMA>(two, dy, -k0)  // multicubic/rectilinear_recursive.rs:447
+                                                 : two * dy - k0;  // multicubic/rectilinear.rs:471, :493, multicubic/rectilinear_recursive.rs:469
       T t = -(x - g[1]) / h01;
       if (sat == OutsideLow && linearize) {
-        if (FMA && fma_linearize) return std::fma(k1, t - one, y1);
+        if (FMA && recursive_arm) return std::fma(k1, t - one, y1);  // multicubic/rectilinear_recursive.rs:482
         T p = k1 * (t - one);
-        return y1 + p;
+        return y1 + p;  // multicubic/rectilinear.rs:500
       }
       return normalized_hermite_spline<FMA>(t, y0, dy, k0, k1);
     }
@@ -210,12 +217,13 @@ inline T cubic_rectilinear_inner(const T* vals, const T* g, T x, Sat sat, bool l
       T h12 = g[2] - g[1];
       T h23 = g[3] - g[2];
       T k0 = centered_difference_nonuniform<FMA>(vals[1], vals[2], vals[3], h12 / h23, one);
-      T k1 = two * dy - k0;
+      T k1 = (recursive_arm && sat == InsideHigh) ? mul_add<FMA>(two, dy, -k0)  // multicubic/rectilinear_recursive.rs:502
+                                                  : two * dy - k0;  // multicubic/rectilinear.rs:515, :532, multicubic/rectilinear_recursive.rs:519
       T t = (x - g[2]) / h23;
       if (sat == OutsideHigh && linearize) {
-        if (FMA && fma_linearize) return std::fma(k1, t - one, y1);
+        if (FMA && recursive_arm) return std::fma(k1, t - one, y1);  // multicubic/rectilinear_recursive.rs:532
         T p = k1 * (t - one);
-        return y1 + p;
+        return y1 + p;  // multicubic/rectilinear.rs:539
       }
       return normalized_hermite_spline<FMA>(t, y0, dy, k0, k1);
     }
@@ -297,7 +305,7 @@ int linear_regular(const size_t* dims, size_t ndims, const T* starts, size_t nst
   auto node = [](const T* v, int d, const Point<T>& q) -> T {
     T y0 = v[0];
     T dy = v[1] - y0;
-    return mul_add<FMA>(q.dts[d], dy, y0);  // regular.rs:378-385
+    return mul_add<FMA>(q.dts[d], dy, y0);  // multilinear/regular.rs:385, :402, multilinear/regular_recursive.rs:384
   };
   for (size_t k = 0; k < nout; ++k) {
     for (int i = 0; i < n; ++i) {
@@ -311,7 +319,7 @@ int linear_regular(const size_t* dims, size_t ndims, const T* starts, size_t nst
       loc = loc < dimmax ? loc : dimmax;  // regular.rs:420-422
       p.origin[i] = (size_t)loc;
       T origin_f = (T)p.origin[i];  // regular.rs:330
-      T index_zero_loc = fma_index ? std::fma(steps[i], origin_f, starts[i])
+      T index_zero_loc = fma_index ? std::fma(steps[i], origin_f, starts[i])  // multilinear/regular.rs:337
                                    : mul_add<false>(steps[i], origin_f, starts[i]);
       p.dts[i] = (x - index_zero_loc) / steps[i];  // regular.rs:339
     }
@@ -347,7 +355,7 @@ int linear_rectilinear(const T* const* grids, const size_t* grid_lens, size_t ng
     T t = (q.x[d] - x0) / step;  // rectilinear.rs:310-313 (recomputed at every node)
     T y0 = v[0];
     T dy = v[1] - y0;
-    return mul_add<FMA>(t, dy, y0);  // rectilinear.rs:318-321
+    return mul_add<FMA>(t, dy, y0);  // multilinear/rectilinear.rs:321, :344, multilinear/rectilinear_recursive.rs:331
   };
   for (size_t k = 0; k < nout; ++k) {
     for (int i = 0; i < n; ++i) {
@@ -443,9 +451,9 @@ int cubic_rectilinear(const T* const* grids, const size_t* grid_lens, size_t ngr
   Point<T> p;
   fill_dimprod(p, grid_lens, n);
   const bool lin = linearize != 0;
-  const bool fma_linearize = n >= 5;  // recursive arm only
-  auto node = [grids, lin, fma_linearize](const T* v, int d, const Point<T>& q) -> T {
-    return cubic_rectilinear_inner<FMA>(v, grids[d] + q.origin[d], q.x[d], q.sat[d], lin, fma_linearize);
+  const bool recursive_arm = n >= 5;  // rectilinear.rs:54-104: N = 1..4 flattened, above that the recursive arm
+  auto node = [grids, lin, recursive_arm](const T* v, int d, const Point<T>& q) -> T {
+    return cubic_rectilinear_inner<FMA>(v, grids[d] + q.origin[d], q.x[d], q.sat[d], lin, recursive_arm);
   };
   for (size_t k = 0; k < nout; ++k) {
     for (int i = 0; i < n; ++i) {
@@ -500,7 +508,7 @@ int nearest_regular(const size_t* dims, size_t ndims, const T* starts, size_t ns
       int64_t loc = iloc > 0 ? iloc : 0;
       loc = loc < dimmax ? loc : dimmax;
       T origin_f = (T)loc;
-      T index_zero_loc = mul_add<FMA>(steps[i], origin_f, starts[i]);  // regular.rs:272-275
+      T index_zero_loc = mul_add<FMA>(steps[i], origin_f, starts[i]);  // nearest/regular.rs:275
       T dt = (x - index_zero_loc) / steps[i];
       size_t offset = (dt <= half) ? 0 : 1;  // regular.rs:283-287 (NaN -> 1)
       idx += ((size_t)loc + offset) * p.dimprod[i];

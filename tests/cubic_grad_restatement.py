@@ -2,8 +2,8 @@
 observation points: both grid kinds, f64 / f32, both `fma` flavours, `linearize_extrapolation` on and off, N = 1..8.
 
 Per point, with every operation rounded in the element type, on the arm of the reference the value path runs (the
-flattened arm of multicubic/regular.rs / rectilinear.rs for N <= 4, the recursive arm for N >= 5; the two differ in two
-fused sites, `k1_plain` and `fma_linear` below):
+flattened arm of multicubic/regular.rs / rectilinear.rs for N <= 4, the recursive arm for N >= 5; the two differ in three
+fused sites, `k1_plain`, `fma_linear` and `k1_fused` below):
 
   per dimension   footprint origin, saturation class (None / Low / High), the linearized flag (outside the grid with
                   linearize_extrapolation) and the local coordinate tt — regular: floc = floor((x - start) / step),
@@ -93,7 +93,7 @@ def locate_rectilinear(x, g, linearize, recursive, dtype):
     none = sat == NONE
     sel = lambda a, b: np.where(none, a, b).astype(dtype)
     return dict(kind="rectilinear", loc=loc, sat=sat, tt=sel(tn, ts), linear=outside & bool(linearize),
-                fma_linear=bool(recursive), r0=sel(r0n, r0s), a0=sel(a0n, np.where(low, w1, wr)), c0=sel(c0n, np.where(low, wr, w1)),
+                fma_linear=bool(recursive), k1_fused=(low | high) & ~outside & bool(recursive), r0=sel(r0n, r0s), a0=sel(a0n, np.where(low, w1, wr)), c0=sel(c0n, np.where(low, wr, w1)),
                 r1=sel(r1n, one), a1=sel(a1n, one), c1=sel(c1n, one), width=sel(h12, ho), ok=np.ones(x.shape, dtype=bool))
 
 
@@ -109,7 +109,7 @@ def _hermite(tt, y0, dy, k0, k1, fma, dtype):
     e2 = c2 + c2
     e3 = three * c3
     if fma:
-        val = _fma(_fma(_fma(c3, tt, c2, dtype), tt, c1, dtype), tt, y0, dtype)
+        val = _fma(_fma(_fma(c3, tt, c2, dtype), tt, c1, dtype), tt, y0, dtype)  # multicubic/mod.rs:89
         der = _fma(_fma(e3, tt, e2, dtype), tt, c1, dtype)
     else:
         val = y0 + tt * (c1 + tt * (c2 + tt * c3))
@@ -132,17 +132,18 @@ def node(dim, v0, v1, v2, v3, fma, dtype):
         k0 = cd / two
         k0 = np.where(low, -k0, k0)
         k1n = (v3 - v1) / two
+        # multicubic/regular.rs:528, :549, :583, :605 and multicubic/regular_recursive.rs:519, :570, :592
         k1e = _mul_add(two, dy, -k0, fma, dtype)
         if fma:
-            k1e = np.where(dim["k1_plain"], two * dy - k0, k1e)  # regular_recursive.rs:536
+            k1e = np.where(dim["k1_plain"], two * dy - k0, k1e)  # multicubic/regular_recursive.rs:536
         k1 = np.where(low | high, k1e, k1n)
-        lin_val = _mul_add(k1, tt - one, ya, fma, dtype)
+        lin_val = _mul_add(k1, tt - one, ya, fma, dtype)  # multicubic/regular.rs:560, :616, multicubic/regular_recursive.rs:547, :603
     else:
         r0, a0, c0, r1, a1, c1 = (dim[k] for k in ("r0", "a0", "c0", "r1", "a1", "c1"))
 
         def combine(a, b, c, dd):
             if fma:
-                return _fma(a, b, c * dd, dtype)
+                return _fma(a, b, c * dd, dtype)  # multicubic/mod.rs:115
             return a * b + c * dd
 
         f01, f12, f23 = v1 - v0, v2 - v1, v3 - v2
@@ -154,7 +155,9 @@ def node(dim, v0, v1, v2, v3, fma, dtype):
         ks = combine(a0, np.where(low, q, f23), c0, np.where(low, f01, q))
         k0s = np.where(low, -ks, ks)
         dys = np.where(low, v0 - v1, f23)
-        k1s = two * dys - k0s
+        k1s = two * dys - k0s  # multicubic/rectilinear.rs:471, :493, :515, :532, multicubic/rectilinear_recursive.rs:469, :519: never fused
+        if fma:  # the recursive arm's InsideLow and InsideHigh: multicubic/rectilinear_recursive.rs:447, :502
+            k1s = np.where(dim["k1_fused"], _fma(two, dys, -k0s, dtype), k1s)
         none = ~(low | high)
         y0 = np.where(high, v2, v1)
         ya = np.where(low, v0, v3)
@@ -162,9 +165,9 @@ def node(dim, v0, v1, v2, v3, fma, dtype):
         k0 = np.where(none, k0n, k0s)
         k1 = np.where(none, k1n, k1s)
         if fma and dim["fma_linear"]:
-            lin_val = _fma(k1, tt - one, ya, dtype)  # rectilinear_recursive.rs:467, :527
+            lin_val = _fma(k1, tt - one, ya, dtype)  # multicubic/rectilinear_recursive.rs:482, :532
         else:
-            lin_val = ya + k1 * (tt - one)  # rectilinear.rs:500, :539: never fused
+            lin_val = ya + k1 * (tt - one)  # multicubic/rectilinear.rs:500, :539: never fused
     val, der = _hermite(tt, y0, dy, k0, k1, fma, dtype)
     lin = dim["linear"]
     return np.where(lin, lin_val, val).astype(dtype), np.where(lin, k1, der).astype(dtype)

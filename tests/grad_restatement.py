@@ -32,6 +32,8 @@ def _mul_add(a, b, c, fma, dtype):
 def _lerp(t, y0, y1, fma, dtype):
     with np.errstate(all="ignore"):
         dy = (y1 - y0).astype(dtype)
+    # multilinear/regular.rs:385, :402, multilinear/regular_recursive.rs:384, multilinear/rectilinear.rs:321, :344,
+    # multilinear/rectilinear_recursive.rs:331
     return _mul_add(t, dy, y0, fma, dtype).astype(dtype)
 
 
@@ -45,7 +47,7 @@ def locate_regular(x, start, step, n, fma, fused_index, dtype):
         ok = (floc >= -(2.0**63)) & (floc < 2.0**63)  # isize::from: NaN and +-inf fail too
         loc = np.clip(np.where(ok, floc, 0.0), 0.0, float(n - 2)).astype(np.int64)
         locf = loc.astype(dtype)
-        if fma and fused_index:
+        if fma and fused_index:  # multilinear/regular.rs:337
             izl = np.asarray(fma_vec(np.full(x.shape, step, dtype=dtype), locf, np.full(x.shape, start, dtype=dtype), dtype),
                              dtype=dtype).reshape(x.shape)
         else:

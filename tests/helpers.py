@@ -400,6 +400,106 @@ def skewed_obs(case, dist, rng, **kw):
     raise ValueError(dist)
 
 
+# ---- the k1 probe: tables on which 2 dy overflows in an end cell while 2 dy - k0 does not -------------------------------------------------
+# The saturated classes of a multicubic axis, in the order of the probe's class codes 0..3; K1_MIDDLE marks the points of the cells
+# between the end cells (class None).
+K1_CLASSES = ("InsideLow", "OutsideLow", "InsideHigh", "OutsideHigh")
+K1_MIDDLE = 4
+# The table along the probed axis, in units of finfo(dtype).max: in both end cells max / 2 < |dy| < max (0.6 and 0.6; 0.6 and 0.55), and
+# the three values an end cell's slopes are taken from keep one trend, so that 2 dy - k0 (1.2 - 0.46 = 0.74 on a uniform axis) is
+# representable although 2 dy is not.  No difference of two values that a node forms reaches max.
+K1_PROFILES = {4: (0.62, 0.02, -0.3, -0.9), 5: (0.62, 0.02, -0.3, -0.35, -0.9)}
+# Intervals of the probed axis on a rectilinear grid, before scaling: the end intervals are the longer ones, because the interior
+# cells' central difference divides an end cell's difference by the ratio (end interval) / (its neighbour) — 0.6 max / 1.25 stays in
+# range, 0.6 max / 0.8 would not.
+K1_INTERVALS = {4: (1.25, 1.0, 1.2), 5: (1.25, 1.0, 0.9, 1.15)}
+
+
+def fma_sites():
+    """tests/golden/fma_sites.json: the reference's fused multiply-add sites ("fused") and their unfused twins ("unfused")."""
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fma_sites.json")) as f:
+        return json.load(f)
+
+
+def k1_expected_fused(kind, n, cls):
+    """From the site table: is `k1 <class>` (cls: index in K1_CLASSES) of multicubic `kind` fused under `fma` in the arm of the
+    reference that serves N = n?  Exactly one row, fused or unfused, must say."""
+    sites = fma_sites()
+    hits = [status for status in ("fused", "unfused") for r in sites[status]
+            if r["method"] == "cubic" and r["kind"] == kind and r["label"] == "k1 " + K1_CLASSES[cls] and r["n"][0] <= n <= r["n"][1]]
+    assert len(hits) == 1, (kind, n, K1_CLASSES[cls], hits)
+    return hits[0] == "fused"
+
+
+def k1_assert_classes(values, cls, kind, n, fma, what=""):
+    """Per class of the probe: finite where the table says fused (under `fma`) and in the middle cells, non-finite elsewhere."""
+    values = np.asarray(values)
+    for c in range(5):
+        at = cls == c
+        assert at.any()
+        finite = np.isfinite(values[at])
+        name = "middle" if c == K1_MIDDLE else K1_CLASSES[c]
+        if c == K1_MIDDLE or (fma and k1_expected_fused(kind, n, c)):
+            assert finite.all(), (what, name, "non-finite results", int((~finite).sum()))
+        else:
+            assert not finite.any(), (what, name, "finite results where 2 dy overflows unfused", int(finite.sum()))
+
+
+def k1_probe_case(kind, shape, axis, dtype, per_class=24, seed=0, linearize=False):
+    """(case, cls): a multicubic case whose table varies along `axis` only (K1_PROFILES times finfo(dtype).max), so that every
+    node of another axis sees four equal values and hands one of them on unchanged, and the result is the 1-D node of `axis` on
+    the profile.  `shape[axis]` is 4 or 5.  Along `axis`, `per_class` points in each of the four saturated classes — inside an
+    end cell, a tenth of its width away from its ends; outside the grid by 0.005 to 0.04 of the end cell's width, where the
+    exact value is still representable — and `per_class` in the cells between (cls == K1_MIDDLE), all shuffled; cls[i] is the
+    index of point i's class in K1_CLASSES.  Every other axis: its own origin and step (regular) or mildly uneven intervals
+    (rectilinear), coordinates uniform inside the grid."""
+    from tests.kat import Case
+
+    dtype = np.dtype(dtype)
+    dt = dtype.type
+    n = len(shape)
+    na = shape[axis]
+    rng = np.random.default_rng(77_000 + 1000 * seed + 100 * n + 10 * axis + (kind == "regular") + 2 * (dtype == np.float32))
+    grids = []
+    for d in range(n):
+        start, step = 0.5 * d - 1.0, 0.25 + 0.125 * d
+        if kind == "regular":
+            g = start + step * np.arange(shape[d])
+        else:
+            h = np.array(K1_INTERVALS[na]) if d == axis else np.ones(shape[d] - 1)
+            h = h * (1.0 + (0.06 if d == axis else 0.3) * (rng.random(h.size) - 0.5))
+            g = start + step * np.concatenate([[0.0], np.cumsum(h)])
+        g = g.astype(dtype)
+        assert np.all(np.diff(g) > 0)
+        grids.append(g)
+    index = [None] * n
+    index[axis] = slice(None)
+    with np.errstate(over="raise"):
+        profile = (np.array(K1_PROFILES[na]) * float(np.finfo(dtype).max)).astype(dtype)
+    vals = np.ascontiguousarray(np.broadcast_to(profile[tuple(index)], shape)).ravel()
+    g64 = grids[axis].astype(np.float64)
+    w_lo, w_hi = g64[1] - g64[0], g64[-1] - g64[-2]
+    u = lambda lo, hi: lo + (hi - lo) * rng.random(per_class)
+    cell = rng.integers(1, na - 2, per_class)
+    xa = np.concatenate([g64[0] + w_lo * u(0.1, 0.9), g64[0] - w_lo * u(0.005, 0.04), g64[-2] + w_hi * u(0.1, 0.9),
+                         g64[-1] + w_hi * u(0.005, 0.04), g64[cell] + (g64[cell + 1] - g64[cell]) * u(0.1, 0.9)])
+    cls = np.repeat(np.arange(5), per_class)
+    order = rng.permutation(cls.size)
+    obs = []
+    for d in range(n):
+        if d == axis:
+            obs.append(np.ascontiguousarray(xa[order].astype(dtype)))
+        else:
+            lo, hi = float(grids[d][0]), float(grids[d][-1])
+            obs.append((lo + (hi - lo) * (0.02 + 0.96 * rng.random(cls.size))).astype(dtype))
+    case = Case(f"k1probe_{kind}_N{n}_a{axis}_{dtype.name}", "cubic", kind, grids, vals, obs, np.zeros(cls.size, dtype=dtype), 0.0,
+                linearize=linearize)
+    return case, cls[order]
+
+
 def rel_err(a, b):
     """|a-b| / max(|b|, 1) — the reference's normalisation (test/test_multicubic_regular.py:97-100)."""
     a = np.asarray(a, dtype=np.float64)

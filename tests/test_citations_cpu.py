@@ -60,17 +60,27 @@ def test_oracle_fma_sites_cite_lines_that_fuse():
     """Lines of the oracle that apply the `fma` flavour (`mul_add<FMA>` / `std::fma` under FMA) and cite a range: the
     reference's text there (a few lines of slack for the `#[cfg(feature = "fma")]` attribute) mentions mul_add."""
     f = os.path.join(ROOT, "oracle", "interpn_oracle.cpp")
-    checked = 0
+    checked = with_module = 0
     for ln, text in enumerate(open(f), 1):
         if "mul_add<FMA>" not in text and "std::fma(" not in text:
             continue
-        for m in CITE.finditer(text.split("//", 1)[1] if "//" in text else ""):
-            path, a, b = m.group(1), int(m.group(2)), int(m.group(3) or m.group(2))
-            ok = False
-            for c in _candidates(path):
-                # lines a-3 .. b+3 (1-based), clipped at the top of the file
-                if any(max(1, a - 3) <= k <= b + 3 for k in REF_FILES[c]["mul_add_lines"]):
-                    ok = True
-            assert ok, (ln, m.group(0))
-            checked += 1
+        comment = text.split("//", 1)[1] if "//" in text else ""
+        for m in CITE.finditer(comment):
+            path = m.group(1)
+            cands = _candidates(path)
+            if "/" in path:  # a citation that names its module means one file of the reference
+                assert len(cands) == 1, (ln, m.group(0), cands)
+                with_module += 1
+            # the citation itself, then the lines that continue it (`, :402`): further lines of the same file
+            more = re.match(r"(?:\s*(?:,|/|and)\s*:\d+(?:-\d+)?)*", comment[m.end():]).group(0)
+            spans = [(int(m.group(2)), int(m.group(3) or m.group(2)))] + [(int(a), int(b or a)) for a, b in re.findall(r":(\d+)(?:-(\d+))?", more)]
+            for a, b in spans:
+                ok = False
+                for c in cands:
+                    # lines a-3 .. b+3 (1-based), clipped at the top of the file
+                    if any(max(1, a - 3) <= k <= b + 3 for k in REF_FILES[c]["mul_add_lines"]):
+                        ok = True
+                assert ok, (ln, m.group(0), a, b)
+                checked += 1
     assert checked >= 4, checked
+    assert with_module >= 12, with_module  # every fused site of the oracle is cited with its module (tests/test_fma_sites_cpu.py)

@@ -76,7 +76,7 @@ def test_cubic_random(oracle, kind, n, linearize, dtype):
 @pytest.mark.parametrize("method,n", [("linear", 7), ("linear", 8), ("cubic", 5), ("cubic", 6), ("cubic", 7)])
 def test_recursive_arms(oracle, monkeypatch, method, kind, n, linearize, form, dtype):
     """N = 7,8 (linear) and 5..8 (cubic) take the reference's recursive arm, with its own FMA
-    sites (regular_recursive.rs:310-313; rectilinear_recursive.rs:467,527).  Served by the
+    sites (regular_recursive.rs:310-313; multicubic/rectilinear_recursive.rs:482, :532).  Served by the
     compile-time-N vertex loop (k_generic_n); the runtime-N kernel must agree bit for bit."""
     if method == "linear" and linearize:
         pytest.skip("linearize_extrapolation is a cubic argument")
