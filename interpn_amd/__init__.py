@@ -13,7 +13,9 @@ from typing import Literal
 
 import numpy as np
 
-from . import _lib, one_dim, raw
+from . import _args, _lib, _setup, one_dim, raw
+from ._setup import check_regular as _check_regular
+from ._setup import is_cuda_tensor as _is_cuda_tensor
 from .classes import (MulticubicRectilinear, MulticubicRegular, MultilinearRectilinear, MultilinearRegular,
                       NearestRectilinear, NearestRegular)
 from .fields import (Fields, fields_lattice_plan, fields_layout, interpn_fields, interpn_fields_grad, interpn_fields_lattice,
@@ -136,10 +138,6 @@ def interpn(
     return out.reshape(outshape)
 
 
-def _is_cuda_tensor(x) -> bool:
-    return type(x).__module__.startswith("torch") and hasattr(x, "is_cuda") and bool(x.is_cuda)
-
-
 def _interpn_on_device(obs, grids, vals, method, out, linearize_extrapolation, assume_regular, check_bounds,
                        bounds_atol):
     """`interpn()` for observation points that already live on the GPU (torch CUDA tensors): same
@@ -147,32 +145,19 @@ def _interpn_on_device(obs, grids, vals, method, out, linearize_extrapolation, a
     optional bounds check), the points and the result never cross PCIe.  Returns a tensor."""
     import torch
 
-    if method not in ("linear", "cubic", "nearest"):
-        raise ValueError(f"Unsupported interpolation configuration: {method}")
+    _setup.check_method(method)
     shape = (out if out is not None else obs[0]).shape
-    obs_t = [x.reshape(-1).contiguous() for x in obs]
-    grids = [np.ascontiguousarray(np.asarray(x).ravel()) for x in grids]
-    vals = vals if _is_cuda_tensor(vals) else np.ascontiguousarray(np.asarray(vals).ravel())
-    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
-    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
-    grids = [g.astype(dtype, copy=False) for g in grids]
-    if _is_cuda_tensor(vals):
-        vals = vals.reshape(-1).contiguous()
-    # The interpolator lives where the points are (not on whatever device happens to be current).
-    device = obs_t[0].device.index if obs_t[0].device.index is not None else torch.cuda.current_device()
+    obs_t = _setup.flat_coords(obs, True)
+    if not _is_cuda_tensor(vals):
+        vals = np.asarray(vals)
+    dtype, grids, vals = _setup.grids_and_values(grids, vals)
+    device = _setup.device_index(obs_t[0])
     if _is_cuda_tensor(vals) and vals.device.index not in (None, device):
         raise ValueError(f"vals is on {vals.device} but the observation points are on cuda:{device}")
-    if assume_regular or _check_regular(grids):
-        starts = np.array([g[0] for g in grids], dtype=dtype)
-        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-        it = Interpolator.regular(method, [len(g) for g in grids], starts, steps, vals,
-                                  linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
-    else:
-        it = Interpolator.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation,
-                                      device=device, dtype=dtype)
+    it, _spec = _setup.interpolator(method, grids, vals, dtype, device, assume_regular, linearize_extrapolation)
     try:
-        if check_bounds and it.check_bounds_tensors(obs_t, bounds_atol).any():
-            raise ValueError("Observation points violate interpolator bounds")
+        if check_bounds:
+            _setup.check_device_bounds(it, obs_t, bounds_atol)
         if out is not None:
             if not out.is_contiguous():
                 raise ValueError("out: expected a contiguous CUDA tensor")
@@ -211,45 +196,15 @@ def interpn_grad(
     cubic = method == "cubic"
     lin = bool(linearize_extrapolation) if cubic else False
     obs = list(obs)
-    grids = [np.ascontiguousarray(np.asarray(x).ravel()) for x in grids]
     on_device = bool(obs) and _is_cuda_tensor(obs[0])
-    if not (_is_cuda_tensor(vals) or isinstance(vals, np.ndarray)):
-        raise TypeError("argument 'vals': expected a numpy array or a torch tensor")
-    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
-    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
-    vals = vals.reshape(-1).contiguous() if _is_cuda_tensor(vals) else np.ascontiguousarray(vals.ravel())
-    grids = [g.astype(dtype, copy=False) for g in grids]
+    dtype, grids, vals = _setup.grids_and_values(grids, vals)
     shape = tuple(obs[0].shape) if obs else (0,)
-    device = -1
-    if on_device:
-        import torch
-
-        device = obs[0].device.index if obs[0].device.index is not None else torch.cuda.current_device()
-        flat = [x.reshape(-1).contiguous() for x in obs]
-    else:
-        flat = [np.ascontiguousarray(np.asarray(x).ravel()) for x in obs]
-    is_regular = assume_regular or _check_regular(grids)
-    if is_regular:
-        dims = [len(g) for g in grids]
-        starts = np.array([g[0] for g in grids], dtype=dtype)
-        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-        it = Interpolator.regular(method, dims, starts, steps, vals, linearize_extrapolation=lin, device=device, dtype=dtype)
-    else:
-        it = Interpolator.rectilinear(method, grids, vals, linearize_extrapolation=lin, device=device, dtype=dtype)
+    device = _setup.device_index(obs[0]) if on_device else -1
+    flat = _setup.flat_coords(obs, on_device)
+    it, spec = _setup.interpolator(method, grids, vals, dtype, device, assume_regular, lin)
     try:
         if check_bounds:
-            if on_device:
-                violated = it.check_bounds_tensors(flat, bounds_atol).any()
-            else:
-                sfx = "f64" if dtype == np.float64 else "f32"
-                outb = np.zeros(len(grids), dtype=bool)
-                if is_regular:
-                    getattr(raw, f"check_bounds_regular_{sfx}")(dims, starts, steps, flat, bounds_atol, outb)
-                else:
-                    getattr(raw, f"check_bounds_rectilinear_{sfx}")(grids, flat, bounds_atol, outb)
-                violated = any(outb)
-            if violated:
-                raise ValueError("Observation points violate interpolator bounds")
+            _setup.check_bounds(it, flat, on_device, grids, spec, dtype, bounds_atol)
         if on_device:
             out, grad = (it.eval_cubic_grad_tensors if cubic else it.eval_grad_tensors)(flat)
             it.finish()
@@ -258,6 +213,32 @@ def interpn_grad(
     finally:
         it.close()
     return out.reshape(shape), grad.reshape((len(flat),) + shape)
+
+
+def _rows_set_up(xi, grids, vals, method, linearize_extrapolation, assume_regular, check_bounds, bounds_atol):
+    """What `interpn_points` and `interpn_points_grad` do before they evaluate: `(interpolator, rows, shape, on_device)`
+    with `xi` of shape `(..., N)` flattened to `(n, N)` rows, `shape` its leading dimensions, and the bounds checked on the
+    unstacked columns.  The caller closes the interpolator."""
+    on_device = _is_cuda_tensor(xi)
+    if not on_device:
+        xi = np.asarray(xi)
+    if len(xi.shape) < 1 or xi.shape[-1] != len(grids):
+        raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+    dtype, grids, vals = _setup.grids_and_values(grids, vals)
+    n = len(grids)
+    device = _setup.device_index(xi) if on_device else -1
+    flat = xi if len(xi.shape) == 2 else xi.reshape(-1, n)
+    if n > 1 and (flat.stride(1) != 1 if on_device else flat.strides[1] != flat.itemsize):  # copied only if it has to be
+        flat = flat.contiguous() if on_device else np.ascontiguousarray(flat)
+    it, spec = _setup.interpolator(method, grids, vals, dtype, device, assume_regular, linearize_extrapolation)
+    try:
+        if check_bounds:
+            cols = [flat[:, d].contiguous() if on_device else np.ascontiguousarray(flat[:, d]) for d in range(n)]
+            _setup.check_bounds(it, cols, on_device, grids, spec, dtype, bounds_atol)
+    except BaseException:
+        it.close()
+        raise
+    return it, flat, tuple(xi.shape[:-1]), on_device
 
 
 def interpn_points(
@@ -279,58 +260,10 @@ def interpn_points(
 
     The rules are those of `interpn()`: dtype from `vals` (`xi` must have it), regular iff every spacing is exactly equal
     or `assume_regular`.  `check_bounds` unstacks the columns for the existing check."""
-    if method not in ("linear", "cubic", "nearest"):
-        raise ValueError(f"Unsupported interpolation configuration: {method}")
-    on_device = _is_cuda_tensor(xi)
-    if not on_device:
-        xi = np.asarray(xi)
-    if len(xi.shape) < 1 or xi.shape[-1] != len(grids):
-        raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
-    if not (_is_cuda_tensor(vals) or isinstance(vals, np.ndarray)):
-        raise TypeError("argument 'vals': expected a numpy array or a torch tensor")
-    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
-    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
-    vals = vals.reshape(-1).contiguous() if _is_cuda_tensor(vals) else np.ascontiguousarray(vals.ravel())
-    grids = [np.ascontiguousarray(np.asarray(x).ravel()).astype(dtype, copy=False) for x in grids]
-    shape = tuple(xi.shape[:-1])
-    n = len(grids)
-    device = -1
-    if on_device:
-        import torch
-
-        device = xi.device.index if xi.device.index is not None else torch.cuda.current_device()
-        flat = xi if xi.dim() == 2 else xi.reshape(-1, n)
-        if n > 1 and flat.stride(1) != 1:
-            flat = flat.contiguous()
-    else:
-        flat = xi if xi.ndim == 2 else xi.reshape(-1, n)
-        if n > 1 and flat.strides[1] != flat.itemsize:
-            flat = np.ascontiguousarray(flat)
-    is_regular = assume_regular or _check_regular(grids)
-    if is_regular:
-        dims = [len(g) for g in grids]
-        starts = np.array([g[0] for g in grids], dtype=dtype)
-        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-        it = Interpolator.regular(method, dims, starts, steps, vals, linearize_extrapolation=linearize_extrapolation,
-                                  device=device, dtype=dtype)
-    else:
-        it = Interpolator.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation, device=device,
-                                      dtype=dtype)
+    _setup.check_method(method)
+    it, flat, shape, on_device = _rows_set_up(xi, grids, vals, method, linearize_extrapolation, assume_regular, check_bounds,
+                                              bounds_atol)
     try:
-        if check_bounds:
-            if on_device:
-                violated = it.check_bounds_tensors([flat[:, d].contiguous() for d in range(n)], bounds_atol).any()
-            else:
-                sfx = "f64" if dtype == np.float64 else "f32"
-                cols = [np.ascontiguousarray(flat[:, d]) for d in range(n)]
-                outb = np.zeros(n, dtype=bool)
-                if is_regular:
-                    getattr(raw, f"check_bounds_regular_{sfx}")(dims, starts, steps, cols, bounds_atol, outb)
-                else:
-                    getattr(raw, f"check_bounds_rectilinear_{sfx}")(grids, cols, bounds_atol, outb)
-                violated = any(outb)
-            if violated:
-                raise ValueError("Observation points violate interpolator bounds")
         if out is not None:
             if on_device and not out.is_contiguous():
                 raise ValueError("out: expected a contiguous CUDA tensor")
@@ -370,54 +303,8 @@ def interpn_points_grad(
     if method not in ("linear", "cubic"):
         raise ValueError(f"interpn_points_grad: method must be \"linear\" or \"cubic\", got {method!r}")
     lin = bool(linearize_extrapolation) if method == "cubic" else False
-    on_device = _is_cuda_tensor(xi)
-    if not on_device:
-        xi = np.asarray(xi)
-    if len(xi.shape) < 1 or xi.shape[-1] != len(grids):
-        raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
-    if not (_is_cuda_tensor(vals) or isinstance(vals, np.ndarray)):
-        raise TypeError("argument 'vals': expected a numpy array or a torch tensor")
-    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
-    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
-    vals = vals.reshape(-1).contiguous() if _is_cuda_tensor(vals) else np.ascontiguousarray(vals.ravel())
-    grids = [np.ascontiguousarray(np.asarray(x).ravel()).astype(dtype, copy=False) for x in grids]
-    shape = tuple(xi.shape[:-1])
-    n = len(grids)
-    device = -1
-    if on_device:
-        import torch
-
-        device = xi.device.index if xi.device.index is not None else torch.cuda.current_device()
-        flat = xi if xi.dim() == 2 else xi.reshape(-1, n)
-        if n > 1 and flat.stride(1) != 1:
-            flat = flat.contiguous()
-    else:
-        flat = xi if xi.ndim == 2 else xi.reshape(-1, n)
-        if n > 1 and flat.strides[1] != flat.itemsize:
-            flat = np.ascontiguousarray(flat)
-    is_regular = assume_regular or _check_regular(grids)
-    if is_regular:
-        dims = [len(g) for g in grids]
-        starts = np.array([g[0] for g in grids], dtype=dtype)
-        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-        it = Interpolator.regular(method, dims, starts, steps, vals, linearize_extrapolation=lin, device=device, dtype=dtype)
-    else:
-        it = Interpolator.rectilinear(method, grids, vals, linearize_extrapolation=lin, device=device, dtype=dtype)
+    it, flat, shape, on_device = _rows_set_up(xi, grids, vals, method, lin, assume_regular, check_bounds, bounds_atol)
     try:
-        if check_bounds:
-            if on_device:
-                violated = it.check_bounds_tensors([flat[:, d].contiguous() for d in range(n)], bounds_atol).any()
-            else:
-                sfx = "f64" if dtype == np.float64 else "f32"
-                cols = [np.ascontiguousarray(flat[:, d]) for d in range(n)]
-                outb = np.zeros(n, dtype=bool)
-                if is_regular:
-                    getattr(raw, f"check_bounds_regular_{sfx}")(dims, starts, steps, cols, bounds_atol, outb)
-                else:
-                    getattr(raw, f"check_bounds_rectilinear_{sfx}")(grids, cols, bounds_atol, outb)
-                violated = any(outb)
-            if violated:
-                raise ValueError("Observation points violate interpolator bounds")
         if on_device:
             res, grad = it.eval_points_grad_tensors(flat)
             it.finish()
@@ -425,7 +312,7 @@ def interpn_points_grad(
             res, grad = it.eval_points_grad_host(flat)
     finally:
         it.close()
-    return res.reshape(shape), grad.reshape(shape + (n,))
+    return res.reshape(shape), grad.reshape(shape + (flat.shape[1],))
 
 
 def interpn_lattice(
@@ -447,45 +334,25 @@ def interpn_lattice(
 
     The rules are those of `interpn()`: inputs ravelled, dtype from `vals`, regular iff every spacing is exactly equal or
     `assume_regular`.  `check_bounds` checks the N vectors (a lattice is inside the grid exactly when each axis is)."""
-    if method not in ("linear", "cubic", "nearest"):
-        raise ValueError(f"Unsupported interpolation configuration: {method}")
-    axes = list(axes)
-    grids = [np.ascontiguousarray(np.asarray(x).ravel()) for x in grids]
+    _setup.check_method(method)
+    axes, grids = list(axes), list(grids)
     if len(axes) != len(grids):
         raise ValueError(f"axes: expected {len(grids)} coordinate vectors (one per grid axis), got {len(axes)}")
     on_device = bool(axes) and _is_cuda_tensor(axes[0])
-    if not (_is_cuda_tensor(vals) or isinstance(vals, np.ndarray)):
-        raise TypeError("argument 'vals': expected a numpy array or a torch tensor")
-    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
-    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
-    vals = vals.reshape(-1).contiguous() if _is_cuda_tensor(vals) else np.ascontiguousarray(vals.ravel())
-    grids = [g.astype(dtype, copy=False) for g in grids]
+    dtype, grids, vals = _setup.grids_and_values(grids, vals)
     shape = tuple(int(a.numel()) if _is_cuda_tensor(a) else int(np.asarray(a).size) for a in axes)
     if out is not None and tuple(out.shape) != shape:
         raise ValueError(f"out: expected shape {shape}, got {tuple(out.shape)}")
-    device = -1
-    if on_device:
-        import torch
-
-        device = axes[0].device.index if axes[0].device.index is not None else torch.cuda.current_device()
-        axes = [a.reshape(-1).contiguous() for a in axes]
-    else:
-        axes = [np.ascontiguousarray(np.asarray(a).ravel()) for a in axes]
-    if assume_regular or _check_regular(grids):
-        starts = np.array([g[0] for g in grids], dtype=dtype)
-        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-        it = Interpolator.regular(method, [len(g) for g in grids], starts, steps, vals,
-                                  linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
-    else:
-        it = Interpolator.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation,
-                                      device=device, dtype=dtype)
+    device = _setup.device_index(axes[0]) if on_device else -1
+    axes = _setup.flat_coords(axes, on_device)
+    it, _spec = _setup.interpolator(method, grids, vals, dtype, device, assume_regular, linearize_extrapolation)
     try:
         if check_bounds:
             # N short batches: axis d is checked against dimension d with the other coordinates held at the grid's origin
             import torch
 
             dev = torch.device("cuda", it.device())
-            tdt = torch.float64 if dtype == np.float64 else torch.float32
+            tdt = _args.torch_dtype(dtype)
             for d, a in enumerate(axes):
                 a_t = a if on_device else torch.from_numpy(a).to(dev)
                 if a_t.numel() == 0:
@@ -493,7 +360,7 @@ def interpn_lattice(
                 batch = [a_t if e == d else torch.full((a_t.numel(),), float(grids[e][0]), dtype=tdt, device=dev)
                          for e in range(len(grids))]
                 if it.check_bounds_tensors(batch, bounds_atol)[d]:
-                    raise ValueError("Observation points violate interpolator bounds")
+                    raise ValueError(_setup.OUT_OF_BOUNDS)
         if on_device:
             res = it.eval_lattice_tensors(axes, out)
             it.finish()
@@ -523,10 +390,3 @@ def lattice_plan(dtype, method: str, dims, axis_lens):
     return _lib.LATTICE_PATHS[path.value], int(lds.value), int(npts.value)
 
 
-def _check_regular(grids) -> bool:
-    """src/interpn/__init__.py:197-203 — exact equality of all spacings."""
-    is_regular = True
-    for grid in grids:
-        dgrid = np.diff(grid)
-        is_regular = is_regular and np.all(dgrid == dgrid[0])
-    return bool(is_regular)

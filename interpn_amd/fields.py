@@ -14,7 +14,9 @@ from ctypes import POINTER, c_double, c_float, c_uint64, c_void_p
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib, _setup
+from ._setup import is_tensor as _is_tensor
+from .handle import Interpolator
 from .raw import _check_arr, _dims, _slice_of_slices
 
 
@@ -55,6 +57,19 @@ def _lattice_out_stride(shape, strides, k, m, layout, contiguous) -> int:
     raise ValueError(f"out: expected a C-contiguous array, or a 2-D ({count}, >= {k}) view with contiguous rows")
 
 
+_ROWS_UNIT = "out: every row must be contiguous (unit stride along the last axis)"  # point-major (n, K) results
+
+
+def _value_row_stride(n: int, strides) -> int:
+    """The element stride between the K rows of a (K, n) result with `strides` (in elements; -1: not a whole number of
+    elements): rows contiguous, any row stride >= n."""
+    if n == 0:
+        return 0
+    if strides[1] != 1 or strides[0] < n:
+        raise ValueError("out: rows must be contiguous")
+    return int(strides[0])
+
+
 def _grad_row_stride(shape, strides) -> int:
     """The one element stride between the K * N rows of a (K, N, n) gradient block of `shape` / `strides` (in elements; -1:
     not a whole number of elements); ValueError for a layout the kernels cannot write."""
@@ -67,10 +82,6 @@ def _grad_row_stride(shape, strides) -> int:
     if row < n or (k > 1 and nd > 1 and strides[0] != nd * row):
         raise ValueError(f"grad: one uniform stride of at least {n} elements between the K * N rows (stride(0) == N * stride(1))")
     return row
-
-
-def _is_tensor(x) -> bool:
-    return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
 
 
 def _field_major(vals, nper, dtype):
@@ -129,8 +140,6 @@ class Fields:
     @classmethod
     def regular(cls, method: str, dims, starts, steps, vals, linearize_extrapolation: bool = False, device: int = -1,
                 dtype=None, fma=None) -> "Fields":
-        from .handle import Interpolator
-
         dtype = np.dtype(dtype or starts.dtype)
         sfx = "f64" if dtype == np.float64 else "f32"
         ct = c_double if dtype == np.float64 else c_float
@@ -150,8 +159,6 @@ class Fields:
     @classmethod
     def rectilinear(cls, method: str, grids, vals, linearize_extrapolation: bool = False, device: int = -1, dtype=None,
                     fma=None) -> "Fields":
-        from .handle import Interpolator
-
         dtype = np.dtype(dtype or grids[0].dtype)
         sfx = "f64" if dtype == np.float64 else "f32"
         gptr, glen, ng, _keep_grids = _slice_of_slices("grids", grids, dtype)
@@ -189,6 +196,17 @@ class Fields:
         self.last_path = "fused" if self.get_option("last_path") == _lib.FIELDS_PATH_FUSED else "per_field"
         return self.last_path
 
+    def _tensor_values(self, out, n: int, want, dev: int):
+        """`(out, row stride)` of the (K, n) values of the device forms: a caller's tensor checked, or a new one."""
+        k = self.nfields
+        if out is None:
+            import torch
+
+            out = torch.empty((k, n), dtype=want, device=torch.device("cuda", dev))
+        elif not (out.is_cuda and out.dim() == 2 and out.dtype == want and tuple(out.shape) == (k, n)):
+            raise TypeError(f"out: expected a ({k}, {n}) {want} CUDA tensor")
+        return out, _value_row_stride(n, out.stride())
+
     # -- evaluation -----------------------------------------------------------------------
     def eval_host(self, obs, out=None) -> np.ndarray:
         """Every field at host points (synchronous): a (K, n) array.  `out` may be a (K, n) array whose rows are
@@ -197,18 +215,13 @@ class Fields:
         n = int(olen[0]) if nobs else 0
         if out is None:
             out = np.zeros((self.nfields, n), dtype=self.dtype)
-        if not isinstance(out, np.ndarray) or out.dtype != self.dtype or out.ndim != 2 or out.shape != (self.nfields, n):
+        if not isinstance(out, np.ndarray) or out.dtype != self.dtype or out.shape != (self.nfields, n):
             raise ValueError(f"out: expected a ({self.nfields}, {n}) array of {self.dtype.name}")
-        item = self.dtype.itemsize
-        if n and (out.strides[1] != item or out.strides[0] % item or out.strides[0] < n * item):
-            raise ValueError("out: rows must be contiguous")
+        stride = _value_row_stride(n, _args.elem_strides(out))
         if not out.flags.writeable:
             raise ValueError("out: array is read-only")
-        vp = (c_void_p * max(nobs, 1))()
-        for i in range(nobs):
-            vp[i] = ctypes.cast(optr[i], c_void_p)
-        stride = out.strides[0] // item if n else 0
-        st = _lib.load().interpn_hip_fields_eval_host(self._h, vp, olen, nobs, c_void_p(out.ctypes.data), max(stride, n), n)
+        vp = _args.void_pp(optr)
+        st = _lib.load().interpn_hip_fields_eval_host(self._h, vp, olen, nobs, c_void_p(out.ctypes.data), stride, n)
         self._took()
         _lib.raise_for_status(st)
         return out
@@ -216,13 +229,10 @@ class Fields:
     def eval_device_ptrs(self, obs_ptrs, out_ptr: int, out_stride: int, npoints: int, stream: int = 0,
                          no_alloc: bool = False) -> str:
         """Enqueue one evaluation on device buffers given as raw addresses; returns the path taken."""
-        n = len(obs_ptrs)
-        vp = (c_void_p * max(n, 1))()
-        for i, p in enumerate(obs_ptrs):
-            vp[i] = c_void_p(int(p))
+        vp = _args.ptr_array(int(p) for p in obs_ptrs)
         path = ctypes.c_int(0)
-        st = _lib.load().interpn_hip_fields_eval_device(self._h, vp, n, c_void_p(int(out_ptr)), int(out_stride), int(npoints),
-                                                        c_void_p(int(stream)), _lib.EVAL_NO_ALLOC if no_alloc else 0,
+        st = _lib.load().interpn_hip_fields_eval_device(self._h, vp, len(obs_ptrs), c_void_p(int(out_ptr)), int(out_stride),
+                                                        int(npoints), c_void_p(int(stream)), _args.eval_flags(no_alloc),
                                                         ctypes.byref(path))
         _lib.raise_for_status(st)
         self.last_path = "fused" if path.value == _lib.FIELDS_PATH_FUSED else "per_field"
@@ -233,30 +243,14 @@ class Fields:
         """Every field at points held in torch CUDA tensors (asynchronous on torch's current stream unless given):
         a (K, n) tensor.  `out` may be a (K, n) tensor with contiguous rows.  Call `finish()` to synchronise and
         surface "Unrepresentable coordinate value"."""
-        import torch
-
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        want = _args.torch_dtype(self.dtype)
         obs = list(obs)
         dev = self.device()
-        for i, t in enumerate(obs):
-            if not (t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
-                raise TypeError(f"obs[{i}]: expected a contiguous 1-D {want} CUDA tensor")
-            if t.device.index not in (None, dev):
-                raise ValueError(f"obs[{i}] is on {t.device} but this set lives on cuda:{dev}")
-        n = obs[0].numel() if obs else 0
-        for t in obs:
-            if t.numel() != n:
-                raise AssertionError("Dimension mismatch")
-        if out is None:
-            out = torch.empty((self.nfields, n), dtype=want, device=torch.device("cuda", dev))
-        elif not (out.is_cuda and out.dim() == 2 and out.dtype == want and tuple(out.shape) == (self.nfields, n)):
-            raise TypeError(f"out: expected a ({self.nfields}, {n}) {want} CUDA tensor")
-        elif n and (out.stride(1) != 1 or out.stride(0) < n):
-            raise ValueError("out: rows must be contiguous")
-        owner = torch.cuda.current_stream(dev) if stream is None else stream
-        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
-        self.eval_device_ptrs([t.data_ptr() for t in obs], out.data_ptr(), max(out.stride(0), n) if n else 0, n, raw, no_alloc)
-        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        n = _args.coord_tensors("obs", obs, want, dev, "set")
+        out, stride = self._tensor_values(out, n, want, dev)
+        raw, owner = _args.resolve_stream(stream, dev)
+        self.eval_device_ptrs([t.data_ptr() for t in obs], out.data_ptr(), stride, n, raw, no_alloc)
+        self._pending_streams[raw] = owner
         return out
 
     # -- values and Jacobian: (K, n) values and (K, N, n) components in one pass --------------
@@ -269,7 +263,7 @@ class Fields:
         value and gradient row."""
         optr, olen, nobs, _keep = _slice_of_slices("obs", obs, self.dtype)
         n = int(olen[0]) if nobs else 0
-        k, nd, item = self.nfields, self._ndims, self.dtype.itemsize
+        k, nd = self.nfields, self._ndims
         if out is None:
             out = np.zeros((k, n), dtype=self.dtype)
         if grad is None:
@@ -278,16 +272,12 @@ class Fields:
             raise ValueError(f"out: expected a ({k}, {n}) array of {self.dtype.name}")
         if not isinstance(grad, np.ndarray) or grad.dtype != self.dtype or grad.shape != (k, nd, n):
             raise ValueError(f"grad: expected a ({k}, {nd}, {n}) array of {self.dtype.name}")
-        if n and (out.strides[1] != item or out.strides[0] % item or out.strides[0] < n * item):
-            raise ValueError("out: rows must be contiguous")
-        gstride = _grad_row_stride(grad.shape, [st // item if st % item == 0 else -1 for st in grad.strides])
+        stride = _value_row_stride(n, _args.elem_strides(out))
+        gstride = _grad_row_stride(grad.shape, _args.elem_strides(grad))
         if not (out.flags.writeable and grad.flags.writeable):
             raise ValueError("out, grad: array is read-only")
-        vp = (c_void_p * max(nobs, 1))()
-        for i in range(nobs):
-            vp[i] = ctypes.cast(optr[i], c_void_p)
-        stride = out.strides[0] // item if n else 0
-        st = _lib.load().interpn_hip_fields_eval_grad_host(self._h, vp, olen, nobs, c_void_p(out.ctypes.data), max(stride, n),
+        vp = _args.void_pp(optr)
+        st = _lib.load().interpn_hip_fields_eval_grad_host(self._h, vp, olen, nobs, c_void_p(out.ctypes.data), stride,
                                                           c_void_p(grad.ctypes.data), max(gstride, n), n)
         self._took()
         _lib.raise_for_status(st)
@@ -296,15 +286,11 @@ class Fields:
     def eval_grad_device_ptrs(self, obs_ptrs, out_ptr: int, out_stride: int, grad_ptr: int, grad_stride: int, npoints: int,
                               stream: int = 0, no_alloc: bool = False) -> str:
         """Enqueue one value-and-Jacobian evaluation on device buffers given as raw addresses; returns the path taken."""
-        n = len(obs_ptrs)
-        vp = (c_void_p * max(n, 1))()
-        for i, p in enumerate(obs_ptrs):
-            vp[i] = c_void_p(int(p))
+        vp = _args.ptr_array(int(p) for p in obs_ptrs)
         path = ctypes.c_int(0)
-        st = _lib.load().interpn_hip_fields_eval_grad_device(self._h, vp, n, c_void_p(int(out_ptr)), int(out_stride),
+        st = _lib.load().interpn_hip_fields_eval_grad_device(self._h, vp, len(obs_ptrs), c_void_p(int(out_ptr)), int(out_stride),
                                                             c_void_p(int(grad_ptr)), int(grad_stride), int(npoints),
-                                                            c_void_p(int(stream)), _lib.EVAL_NO_ALLOC if no_alloc else 0,
-                                                            ctypes.byref(path))
+                                                            c_void_p(int(stream)), _args.eval_flags(no_alloc), ctypes.byref(path))
         _lib.raise_for_status(st)
         self.last_path = "fused" if path.value == _lib.FIELDS_PATH_FUSED else "per_field"
         self._pending_streams.setdefault(int(stream), None)
@@ -317,38 +303,23 @@ class Fields:
         `last_path` says which path ran.  `out`: rows contiguous, any row stride >= n; `grad`: unit stride along its last
         axis and one uniform stride >= n between its K * N rows.  Call `finish()` to synchronise and surface
         "Unrepresentable coordinate value"."""
-        import torch
-
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        want = _args.torch_dtype(self.dtype)
         obs = list(obs)
         dev = self.device()
-        for i, t in enumerate(obs):
-            if not (t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
-                raise TypeError(f"obs[{i}]: expected a contiguous 1-D {want} CUDA tensor")
-            if t.device.index not in (None, dev):
-                raise ValueError(f"obs[{i}] is on {t.device} but this set lives on cuda:{dev}")
-        n = obs[0].numel() if obs else 0
-        for t in obs:
-            if t.numel() != n:
-                raise AssertionError("Dimension mismatch")
+        n = _args.coord_tensors("obs", obs, want, dev, "set")
         k, nd = self.nfields, self._ndims
-        where = torch.device("cuda", dev)
-        if out is None:
-            out = torch.empty((k, n), dtype=want, device=where)
-        elif not (out.is_cuda and out.dim() == 2 and out.dtype == want and tuple(out.shape) == (k, n)):
-            raise TypeError(f"out: expected a ({k}, {n}) {want} CUDA tensor")
-        elif n and (out.stride(1) != 1 or out.stride(0) < n):
-            raise ValueError("out: rows must be contiguous")
+        out, stride = self._tensor_values(out, n, want, dev)
         if grad is None:
-            grad = torch.empty((k, nd, n), dtype=want, device=where)
+            import torch
+
+            grad = torch.empty((k, nd, n), dtype=want, device=torch.device("cuda", dev))
         elif not (grad.is_cuda and grad.dim() == 3 and grad.dtype == want and tuple(grad.shape) == (k, nd, n)):
             raise TypeError(f"grad: expected a ({k}, {nd}, {n}) {want} CUDA tensor")
         gstride = _grad_row_stride(tuple(grad.shape), grad.stride())
-        owner = torch.cuda.current_stream(dev) if stream is None else stream
-        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
-        self.eval_grad_device_ptrs([t.data_ptr() for t in obs], out.data_ptr(), max(out.stride(0), n) if n else 0, grad.data_ptr(),
+        raw, owner = _args.resolve_stream(stream, dev)
+        self.eval_grad_device_ptrs([t.data_ptr() for t in obs], out.data_ptr(), stride, grad.data_ptr(),
                                    max(gstride, n) if n else 0, n, raw, no_alloc)
-        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        self._pending_streams[raw] = owner
         return out, grad
 
     def eval_grad(self, obs, out=None, grad=None, **kwargs):
@@ -378,10 +349,7 @@ class Fields:
         stride is a whole number of elements (`buf[:, :3]` of an `(n, 4)` array), is taken as it is; anything else is
         copied once.  `out` may have any row stride >= K with unit-stride rows; elements behind a row's first K are not
         touched.  On "Unrepresentable coordinate value" exactly the rows in front of the failing point are written."""
-        if not isinstance(pts, np.ndarray):
-            raise TypeError(f"argument 'pts': expected a numpy array, got {type(pts).__name__}")
-        if pts.dtype != self.dtype:
-            raise TypeError(f"argument 'pts': expected dtype {self.dtype.name}, got {pts.dtype.name}")
+        _args.check_ndarray("pts", pts, self.dtype)
         nd, k, item = self._ndims, self.nfields, self.dtype.itemsize
         if pts.ndim < 1 or pts.shape[-1] != nd:
             raise ValueError(f"argument 'pts': expected shape (..., {nd}), got {tuple(pts.shape)}")
@@ -402,11 +370,8 @@ class Fields:
         if not out.flags.writeable:
             raise ValueError("out: array is read-only")
         if out.ndim == 2:
-            if n and k > 1 and out.strides[1] != item:
-                raise ValueError("out: every row must be contiguous (unit stride along the last axis)")
-            if n > 1 and (out.strides[0] % item or out.strides[0] < k * item):
-                raise ValueError(f"out: the row stride must be a whole number of elements, at least {k}")
-            ostride = out.strides[0] // item if n > 1 else k
+            ostride = _args.row_stride("out", n, k, _args.elem_strides(out), ValueError, _ROWS_UNIT,
+                                       "out: the row stride must be a whole number of elements, at least {width}", check_empty=False)
         else:
             if not out.flags.c_contiguous:
                 raise ValueError("out: expected a C-contiguous array, or a 2-D array with contiguous rows")
@@ -422,17 +387,14 @@ class Fields:
         `interpn_hip_fields_eval_points_device`): no `pts.T.contiguous()` in front and no transpose of the result behind.
         `pts` and `out` must not overlap.  Sets with the fused table run one kernel, which can be captured into a graph;
         `last_points_path` says which path ran; `finish()` synchronises and surfaces "Unrepresentable coordinate value"."""
-        import torch
-
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        want = _args.torch_dtype(self.dtype)
         nd, k = self._ndims, self.nfields
         if not (hasattr(pts, "is_cuda") and pts.is_cuda and pts.dtype == want):
             raise TypeError(f"pts: expected a {want} CUDA tensor of shape (..., {nd})")
         if pts.dim() < 1 or pts.shape[-1] != nd:
             raise ValueError(f"pts: expected shape (..., {nd}), got {tuple(pts.shape)}")
         dev = self.device()
-        if pts.device.index not in (None, dev):
-            raise ValueError(f"pts is on {pts.device} but this set lives on cuda:{dev}")
+        _args.same_device("pts", pts, dev, "set")
         lead = tuple(pts.shape[:-1])
         if pts.dim() == 2 and (nd == 1 or pts.stride(1) == 1) and (pts.shape[0] <= 1 or pts.stride(0) >= nd):
             rows = pts
@@ -441,33 +403,30 @@ class Fields:
         n = int(rows.shape[0])
         stride = int(rows.stride(0)) if n > 1 else nd
         if out is None:
+            import torch
+
             out = torch.empty(lead + (k,), dtype=want, device=torch.device("cuda", dev))
         if not (hasattr(out, "is_cuda") and out.is_cuda and out.dtype == want):
             raise TypeError(f"out: expected a {want} CUDA tensor")
         if tuple(out.shape) != lead + (k,):
             raise ValueError(f"out: expected shape {lead + (k,)}, got {tuple(out.shape)}")
-        if out.device.index not in (None, dev):
-            raise ValueError(f"out is on {out.device} but this set lives on cuda:{dev}")
+        _args.same_device("out", out, dev, "set")
         if out.dim() == 2:
-            if n and k > 1 and out.stride(1) != 1:
-                raise ValueError("out: every row must be contiguous (unit stride along the last axis)")
-            if n > 1 and out.stride(0) < k:
-                raise ValueError(f"out: the row stride must be at least {k}")
-            ostride = int(out.stride(0)) if n > 1 else k
+            ostride = _args.row_stride("out", n, k, out.stride(), ValueError, _ROWS_UNIT, "out: the row stride must be at least {width}",
+                                       check_empty=False)
         else:
             if not out.is_contiguous():
                 raise ValueError("out: expected a contiguous tensor, or a 2-D tensor with contiguous rows")
             ostride = k
-        owner = torch.cuda.current_stream(dev) if stream is None else stream
-        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        raw, owner = _args.resolve_stream(stream, dev)
         path = ctypes.c_int(0)
         st = _lib.load().interpn_hip_fields_eval_points_device(self._h, c_void_p(rows.data_ptr()), stride, n, c_void_p(out.data_ptr()),
-                                                              ostride, c_void_p(int(raw)), _lib.EVAL_NO_ALLOC if no_alloc else 0,
+                                                              ostride, c_void_p(int(raw)), _args.eval_flags(no_alloc),
                                                               ctypes.byref(path))
         _lib.raise_for_status(st)
         if n:
             self._took_points()
-        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        self._pending_streams[raw] = owner
         return out
 
     def eval_points(self, pts, out=None, **kwargs):
@@ -507,26 +466,17 @@ class Fields:
         k, item = self.nfields, self.dtype.itemsize
         if out is None:
             out = np.zeros((k,) + m if field_axis == 0 else m + (k,), dtype=self.dtype)
-        if not isinstance(out, np.ndarray):
-            raise TypeError(f"argument 'out': expected a numpy array, got {type(out).__name__}")
-        if out.dtype != self.dtype:
-            raise TypeError(f"argument 'out': expected dtype {self.dtype.name}, got {out.dtype.name}")
+        _args.check_ndarray("out", out, self.dtype)
         if any(st % item for st in out.strides):
             raise ValueError("out: strides must be whole numbers of elements")
         stride = _lattice_out_stride(out.shape, [st // item for st in out.strides], k, m, layout, out.flags.c_contiguous)
         if not out.flags.writeable:
             raise ValueError("argument 'out': array is read-only")
-        vp = (c_void_p * max(naxes, 1))()
-        for i in range(naxes):
-            vp[i] = ctypes.cast(aptr[i], c_void_p)
+        vp = _args.void_pp(aptr)
         bad = c_uint64(0)
         st = _lib.load().interpn_hip_fields_eval_lattice_host(self._h, vp, alen, naxes, c_void_p(out.ctypes.data), stride, layout,
                                                              ctypes.byref(bad))
-        if st in _lib.UNREPRESENTABLE:
-            err = AssertionError(_lib.strerror(st))
-            err.first_bad_index = bad.value
-            raise err
-        _lib.raise_for_status(st)
+        _args.raise_for_indexed_status(st, bad)
         return out
 
     def eval_lattice_tensors(self, axes, out=None, field_axis: int = 0, stream=None, no_alloc: bool = False):
@@ -534,37 +484,30 @@ class Fields:
         `interpn_hip_fields_eval_lattice_device`): `axes` are contiguous 1-D tensors of the set's dtype.  `out` must not
         overlap them.  `last_lattice_path` says which path ran; `finish()` synchronises and raises for a coordinate the
         reference cannot evaluate, with `first_bad_index` in C order over m (the same for every field)."""
-        import torch
-
         layout = _field_axis(field_axis)
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        want = _args.torch_dtype(self.dtype)
         axes = list(axes)
         dev = self.device() if self._h is not None and self._h.value else -1
-        for i, t in enumerate(axes):
-            if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
-                raise TypeError(f"axes[{i}]: expected a contiguous 1-D {want} CUDA tensor")
-            if t.device.index not in (None, dev):
-                raise ValueError(f"axes[{i}] is on {t.device} but this set lives on cuda:{dev}")
+        _args.coord_tensors("axes", axes, want, dev, "set", same_length=False)
         m = tuple(int(t.numel()) for t in axes)
         k = self.nfields
         if out is None:
+            import torch
+
             out = torch.empty((k,) + m if field_axis == 0 else m + (k,), dtype=want, device=torch.device("cuda", dev))
         if not (hasattr(out, "is_cuda") and out.is_cuda and out.dtype == want):
             raise TypeError(f"out: expected a {want} CUDA tensor")
-        if out.device.index not in (None, dev):
-            raise ValueError(f"out is on {out.device} but this set lives on cuda:{dev}")
+        _args.same_device("out", out, dev, "set")
         stride = _lattice_out_stride(out.shape, out.stride(), k, m, layout, out.is_contiguous())
-        owner = torch.cuda.current_stream(dev) if stream is None else stream
-        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        raw, owner = _args.resolve_stream(stream, dev)
         n = len(axes)
-        vp = (c_void_p * max(n, 1))(*[t.data_ptr() for t in axes])
         lens = (ctypes.c_size_t * max(n, 1))(*m)
         path = ctypes.c_int(0)
-        st = _lib.load().interpn_hip_fields_eval_lattice_device(self._h, vp, lens, n, c_void_p(out.data_ptr()), stride, layout,
-                                                               c_void_p(int(raw)), _lib.EVAL_NO_ALLOC if no_alloc else 0,
-                                                               ctypes.byref(path))
+        st = _lib.load().interpn_hip_fields_eval_lattice_device(self._h, _args.ptr_array(t.data_ptr() for t in axes), lens, n,
+                                                               c_void_p(out.data_ptr()), stride, layout, c_void_p(int(raw)),
+                                                               _args.eval_flags(no_alloc), ctypes.byref(path))
         _lib.raise_for_status(st)
-        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        self._pending_streams[raw] = owner
         return out
 
     def eval_lattice(self, axes, out=None, **kwargs):
@@ -580,26 +523,8 @@ class Fields:
     def finish(self, stream=None) -> None:
         """Wait for the evaluations enqueued since the last finish; AssertionError("Unrepresentable coordinate
         value") with `.first_bad_index` if a point could not be evaluated (the same index for every field)."""
-        lib = _lib.load()
-        if stream is not None:
-            raws = [stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)]
-        else:
-            raws = list(self._pending_streams) or [0]
-        first_bad, bad_status, status = None, _lib.ERR_UNREPRESENTABLE, _lib.OK
-        for raw in raws:
-            bad = c_uint64(0)
-            st = lib.interpn_hip_fields_finish(self._h, c_void_p(int(raw)), ctypes.byref(bad))
-            self._pending_streams.pop(raw, None)
-            if st in _lib.UNREPRESENTABLE:
-                bad_status = st
-                first_bad = bad.value if first_bad is None else min(first_bad, bad.value)
-            elif st != _lib.OK and status == _lib.OK:
-                status = st
-        _lib.raise_for_status(status)
-        if first_bad is not None:
-            err = AssertionError(_lib.strerror(bad_status))
-            err.first_bad_index = first_bad
-            raise err
+        raws = [_args.resolve_stream(stream, None)[0]] if stream is not None else list(self._pending_streams) or [0]
+        _args.finish_streams(_lib.load().interpn_hip_fields_finish, self._h, raws, self._pending_streams)
 
     def close(self) -> None:
         if self._h is not None and self._h.value:
@@ -648,50 +573,20 @@ def interpn_fields_lattice(axes, grids, vals, *, method="linear", field_axis: in
 
     `vals` has shape (K, *dims) and the result (K, *m), m = the vectors' lengths; with `field_axis=-1` the channel-last
     layout: `vals` (*dims, K), result (*m, K) — an image resize when N = 2."""
-    from . import _check_regular, _is_cuda_tensor
-
     _field_axis(field_axis)
-    if method not in ("linear", "cubic", "nearest"):
-        raise ValueError(f"Unsupported interpolation configuration: {method}")
-    if not (isinstance(vals, np.ndarray) or _is_tensor(vals)):
-        raise TypeError("vals: expected a numpy array or a torch tensor with a field axis")
-    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
-    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
-    if len(vals.shape) < 2:
-        raise ValueError("vals: expected a field axis besides the grid's values")
+    _setup.check_method(method)
     axes = list(axes)
-    grids = [np.ascontiguousarray(np.asarray(g).ravel()).astype(dtype, copy=False) for g in grids]
-    if len(axes) != len(grids):
-        raise ValueError(f"axes: expected {len(grids)} coordinate vectors (one per grid axis), got {len(axes)}")
-    nper = int(np.prod([g.size for g in grids], dtype=object))
-    k = int(vals.shape[field_axis])
-    if k * nper != int(np.prod(tuple(vals.shape), dtype=object)):
-        raise ValueError(f"vals: expected {k} x {nper} values for grids of {[g.size for g in grids]}, got shape {tuple(vals.shape)}")
-    if field_axis == -1:  # (*dims, K) -> (K, prod(dims)), once: set-up, not part of the pass over the lattice
-        vals = vals.reshape(nper, k).T
-    vals = (vals.contiguous() if _is_tensor(vals) else np.ascontiguousarray(vals)).reshape(k, nper)
-    on_device = bool(axes) and _is_cuda_tensor(axes[0])
+    dtype, grids, k, nper = _setup.grids_and_fields(grids, vals, field_axis, naxes=len(axes))
+    on_device = bool(axes) and _setup.is_cuda_tensor(axes[0])
     m = tuple(int(a.numel()) if _is_tensor(a) else int(np.asarray(a).size) for a in axes)
     rshape = (k,) + m if field_axis == 0 else m + (k,)
     if out is not None and tuple(out.shape) != rshape:
         raise ValueError(f"out: expected shape {rshape}, got {tuple(out.shape)}")
-    device = -1
-    if on_device:
-        import torch
-
-        device = axes[0].device.index if axes[0].device.index is not None else torch.cuda.current_device()
-        axes = [a.reshape(-1).contiguous() for a in axes]
-    else:
-        if _is_tensor(vals):
-            vals = vals.cpu().numpy()
-        axes = [np.ascontiguousarray(np.asarray(a).ravel()) for a in axes]
-    if assume_regular or _check_regular(grids):
-        starts = np.array([g[0] for g in grids], dtype=dtype)
-        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-        fs = Fields.regular(method, [g.size for g in grids], starts, steps, vals, linearize_extrapolation=linearize_extrapolation,
-                            device=device, dtype=dtype)
-    else:
-        fs = Fields.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
+    device = _setup.device_index(axes[0]) if on_device else -1
+    axes = _setup.flat_coords(axes, on_device)
+    vals = _setup.field_major(vals, k, nper, field_axis == -1, on_device)
+    fs = _setup.create(Fields, method, grids, _setup.regular_spec(grids, dtype, assume_regular), vals, dtype, device,
+                       linearize_extrapolation=linearize_extrapolation)
     try:
         if on_device:
             res = fs.eval_lattice_tensors(axes, out, field_axis=field_axis)
@@ -703,6 +598,17 @@ def interpn_fields_lattice(axes, grids, vals, *, method="linear", field_axis: in
     return res
 
 
+def _points_of_fields(obs, grids, vals, method, field_axis):
+    """What `interpn_fields` and `interpn_fields_grad` check and work out before they differ:
+    `(dtype, grids, k, nper, on_device, pshape)`."""
+    _field_axis(field_axis)
+    _setup.check_method(method)
+    dtype, grids, k, nper = _setup.grids_and_fields(grids, vals, field_axis)
+    on_device = bool(len(obs)) and _setup.is_cuda_tensor(obs[0])
+    pshape = tuple(obs[0].shape) if len(obs) else (0,)
+    return dtype, grids, k, nper, on_device, pshape
+
+
 def interpn_fields(obs, grids, vals, *, method="linear", field_axis: int = 0, out=None, linearize_extrapolation: bool = True,
                    assume_regular: bool = False, check_bounds: bool = False, bounds_atol: float = 1e-8):
     """`interpn()` for K fields on one grid: the same rules (ravelled inputs, dtype from `vals`, exact-spacing
@@ -710,73 +616,21 @@ def interpn_fields(obs, grids, vals, *, method="linear", field_axis: int = 0, ou
 
     `vals` has shape (K, *dims) and the result (K, *obs[0].shape); with `field_axis=-1` the scipy layout:
     `vals` (*dims, K), result (*obs[0].shape, K)."""
-    from . import _check_regular, _is_cuda_tensor, raw
-
-    if field_axis not in (0, -1):
-        raise ValueError("field_axis: expected 0 (fields first) or -1 (fields last)")
-    if method not in ("linear", "cubic", "nearest"):
-        raise ValueError(f"Unsupported interpolation configuration: {method}")
-    if not (isinstance(vals, np.ndarray) or _is_tensor(vals)):
-        raise TypeError("vals: expected a numpy array or a torch tensor with a field axis")
-    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
-    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
-    if len(vals.shape) < 2:
-        raise ValueError("vals: expected a field axis besides the grid's values")
-    grids = [np.ascontiguousarray(np.asarray(g).ravel()).astype(dtype, copy=False) for g in grids]
-    nper = int(np.prod([g.size for g in grids], dtype=object))
-    k = int(vals.shape[field_axis])
-    if k * nper != int(np.prod(tuple(vals.shape), dtype=object)):
-        raise ValueError(f"vals: expected {k} x {nper} values for grids of {[g.size for g in grids]}, got shape {tuple(vals.shape)}")
-    if field_axis == -1:  # (*dims, K) -> (K, prod(dims))
-        vals = vals.reshape(nper, k).T
-    vals = (vals.contiguous() if _is_tensor(vals) else np.ascontiguousarray(vals)).reshape(k, nper)
-
-    on_device = bool(len(obs)) and _is_cuda_tensor(obs[0])
-    pshape = tuple(obs[0].shape) if len(obs) else (0,)
+    dtype, grids, k, nper, on_device, pshape = _points_of_fields(obs, grids, vals, method, field_axis)
     rshape = (k,) + pshape if field_axis == 0 else pshape + (k,)
     if out is not None and tuple(out.shape) != rshape:
         raise ValueError(f"out: expected shape {rshape}, got {tuple(out.shape)}")
-    regular = assume_regular or _check_regular(grids)
-    device = -1
-    if on_device:
-        import torch
-
-        device = obs[0].device.index if obs[0].device.index is not None else torch.cuda.current_device()
-        obs_flat = [x.reshape(-1).contiguous() for x in obs]
-    else:
-        if _is_tensor(vals):
-            vals = vals.cpu().numpy()
-        obs_flat = [np.ascontiguousarray(np.asarray(x).ravel()) for x in obs]
-    if regular:
-        dims = [g.size for g in grids]
-        starts = np.array([g[0] for g in grids], dtype=dtype)
-        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-    sfx = "f64" if dtype == np.float64 else "f32"
+    device = _setup.device_index(obs[0]) if on_device else -1
+    obs_flat = _setup.flat_coords(obs, on_device)
+    vals = _setup.field_major(vals, k, nper, field_axis == -1, on_device)
+    spec = _setup.regular_spec(grids, dtype, assume_regular)
     if check_bounds and not on_device:
-        outb = np.zeros(len(grids), dtype=bool)
-        if regular:
-            getattr(raw, f"check_bounds_regular_{sfx}")(dims, starts, steps, obs_flat, bounds_atol, outb)
-        else:
-            getattr(raw, f"check_bounds_rectilinear_{sfx}")(grids, obs_flat, bounds_atol, outb)
-        if any(outb):
-            raise ValueError("Observation points violate interpolator bounds")
-    if regular:
-        fs = Fields.regular(method, dims, starts, steps, vals, linearize_extrapolation=linearize_extrapolation, device=device,
-                            dtype=dtype)
-    else:
-        fs = Fields.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
+        _setup.check_host_bounds(grids, spec, dtype, obs_flat, bounds_atol)
+    fs = _setup.create(Fields, method, grids, spec, vals, dtype, device, linearize_extrapolation=linearize_extrapolation)
     try:
         if on_device:
-            if check_bounds:  # the bounds are the grid's: any one field's interpolator checks them on the device
-                from .handle import Interpolator
-
-                one = (Interpolator.regular(method, dims, starts, steps, vals[0], device=device, dtype=dtype) if regular
-                       else Interpolator.rectilinear(method, grids, vals[0], device=device, dtype=dtype))
-                try:
-                    if one.check_bounds_tensors(obs_flat, bounds_atol).any():
-                        raise ValueError("Observation points violate interpolator bounds")
-                finally:
-                    one.close()
+            if check_bounds:
+                _setup.check_field_device_bounds(method, grids, spec, vals, dtype, device, obs_flat, bounds_atol)
             direct = out is not None and field_axis == 0 and out.is_contiguous()
             res = fs.eval_tensors(obs_flat, out.reshape(k, -1) if direct else None)
             fs.finish()
@@ -810,46 +664,13 @@ def interpn_fields_grad(obs, grids, vals, *, method="linear", field_axis: int = 
     derivative of field f with respect to coordinate d, with the bits of `interpn_grad` of field f.  With `field_axis=-1`
     the scipy layout: `vals` (*dims, K), `out` (*obs[0].shape, K), `jac` (*obs[0].shape, K, N) — permuted copies made here,
     not by the kernel."""
-    from . import _check_regular, _is_cuda_tensor
-
-    if field_axis not in (0, -1):
-        raise ValueError("field_axis: expected 0 (fields first) or -1 (fields last)")
-    if method not in ("linear", "cubic", "nearest"):
-        raise ValueError(f"Unsupported interpolation configuration: {method}")
-    if not (isinstance(vals, np.ndarray) or _is_tensor(vals)):
-        raise TypeError("vals: expected a numpy array or a torch tensor with a field axis")
-    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
-    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
-    if len(vals.shape) < 2:
-        raise ValueError("vals: expected a field axis besides the grid's values")
-    grids = [np.ascontiguousarray(np.asarray(g).ravel()).astype(dtype, copy=False) for g in grids]
-    nper = int(np.prod([g.size for g in grids], dtype=object))
-    k = int(vals.shape[field_axis])
-    if k * nper != int(np.prod(tuple(vals.shape), dtype=object)):
-        raise ValueError(f"vals: expected {k} x {nper} values for grids of {[g.size for g in grids]}, got shape {tuple(vals.shape)}")
-    if field_axis == -1:  # (*dims, K) -> (K, prod(dims))
-        vals = vals.reshape(nper, k).T
-    vals = (vals.contiguous() if _is_tensor(vals) else np.ascontiguousarray(vals)).reshape(k, nper)
-    on_device = bool(len(obs)) and _is_cuda_tensor(obs[0])
-    pshape = tuple(obs[0].shape) if len(obs) else (0,)
+    dtype, grids, k, nper, on_device, pshape = _points_of_fields(obs, grids, vals, method, field_axis)
     nd = len(grids)
-    device = -1
-    if on_device:
-        import torch
-
-        device = obs[0].device.index if obs[0].device.index is not None else torch.cuda.current_device()
-        obs_flat = [x.reshape(-1).contiguous() for x in obs]
-    else:
-        if _is_tensor(vals):
-            vals = vals.cpu().numpy()
-        obs_flat = [np.ascontiguousarray(np.asarray(x).ravel()) for x in obs]
-    if assume_regular or _check_regular(grids):
-        starts = np.array([g[0] for g in grids], dtype=dtype)
-        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-        fs = Fields.regular(method, [g.size for g in grids], starts, steps, vals, linearize_extrapolation=linearize_extrapolation,
-                            device=device, dtype=dtype)
-    else:
-        fs = Fields.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
+    device = _setup.device_index(obs[0]) if on_device else -1
+    obs_flat = _setup.flat_coords(obs, on_device)
+    vals = _setup.field_major(vals, k, nper, field_axis == -1, on_device)
+    fs = _setup.create(Fields, method, grids, _setup.regular_spec(grids, dtype, assume_regular), vals, dtype, device,
+                       linearize_extrapolation=linearize_extrapolation)
     try:
         if on_device:
             out, jac = fs.eval_grad_tensors(obs_flat)
@@ -874,17 +695,11 @@ def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, lineari
     (..., N) — a numpy array or a torch CUDA tensor — and a result of shape (..., K).  The rules are those of
     `interpn_fields` (dtype from `vals`, exact-spacing regularity test); the points and the result keep their layout
     (`Fields.eval_points`), and the value table is re-laid field-major once, as part of setting the fields up."""
-    from . import _check_regular, _is_cuda_tensor, raw
-
-    if method not in ("linear", "cubic", "nearest"):
-        raise ValueError(f"Unsupported interpolation configuration: {method}")
-    if not (isinstance(vals, np.ndarray) or _is_tensor(vals)):
-        raise TypeError("vals: expected a numpy array or a torch tensor with a trailing field axis")
-    assert str(vals.dtype).endswith(("float64", "float32")), "`interpn` defined only for float32 and float64 data"
-    dtype = np.dtype(np.float64 if str(vals.dtype).endswith("64") else np.float32)
+    _setup.check_method(method)
+    dtype = _setup.field_values_dtype(vals, "a trailing field axis")
     if not (isinstance(xi, np.ndarray) or _is_tensor(xi)):
         raise TypeError("xi: expected a numpy array or a torch tensor of shape (..., N)")
-    grids = [np.ascontiguousarray(np.asarray(g).ravel()).astype(dtype, copy=False) for g in grids]
+    grids = _setup.canonical_grids(grids, dtype)
     nd = len(grids)
     if len(vals.shape) != nd + 1:
         raise ValueError(f"vals: expected shape (*dims, K) for {nd} grids, got {tuple(vals.shape)}")
@@ -893,8 +708,8 @@ def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, lineari
     nper = int(np.prod([g.size for g in grids], dtype=object))
     k = int(vals.shape[-1])
     if tuple(int(v) for v in vals.shape[:-1]) != tuple(g.size for g in grids) or k < 1:
-        raise ValueError(f"vals: expected {k} x {nper} values for grids of {[g.size for g in grids]}, got shape {tuple(vals.shape)}")
-    on_device = _is_cuda_tensor(xi)
+        raise _setup.value_count_error(k, nper, grids, vals)
+    on_device = _setup.is_cuda_tensor(xi)
     want = str(xi.dtype).rsplit(".", 1)[-1]
     if want != dtype.name:
         raise TypeError(f"xi: expected dtype {dtype.name} (that of vals), got {want}")
@@ -903,49 +718,17 @@ def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, lineari
         raise ValueError(f"out: expected shape {rshape}, got {tuple(out.shape)}")
     if _is_tensor(xi) and not on_device:
         raise TypeError("xi: expected a numpy array or a torch CUDA tensor")
-    # (*dims, K) -> (K, prod(dims)), once: set-up, not part of the pass over the points
-    vals = vals.reshape(nper, k).T
-    vals = (vals.contiguous() if _is_tensor(vals) else np.ascontiguousarray(vals)).reshape(k, nper)
-    regular = assume_regular or _check_regular(grids)
-    device = -1
-    if on_device:
-        import torch
-
-        device = xi.device.index if xi.device.index is not None else torch.cuda.current_device()
-    elif _is_tensor(vals):
-        vals = vals.cpu().numpy()
-    if regular:
-        dims = [g.size for g in grids]
-        starts = np.array([g[0] for g in grids], dtype=dtype)
-        steps = np.array([g[1] - g[0] for g in grids], dtype=dtype)
-    sfx = "f64" if dtype == np.float64 else "f32"
+    device = _setup.device_index(xi) if on_device else -1
+    vals = _setup.field_major(vals, k, nper, True, on_device)
+    spec = _setup.regular_spec(grids, dtype, assume_regular)
     if check_bounds and not on_device:
-        cols = [np.ascontiguousarray(xi[..., d].ravel()) for d in range(nd)]
-        outb = np.zeros(nd, dtype=bool)
-        if regular:
-            getattr(raw, f"check_bounds_regular_{sfx}")(dims, starts, steps, cols, bounds_atol, outb)
-        else:
-            getattr(raw, f"check_bounds_rectilinear_{sfx}")(grids, cols, bounds_atol, outb)
-        if any(outb):
-            raise ValueError("Observation points violate interpolator bounds")
-    if regular:
-        fs = Fields.regular(method, dims, starts, steps, vals, linearize_extrapolation=linearize_extrapolation, device=device,
-                            dtype=dtype)
-    else:
-        fs = Fields.rectilinear(method, grids, vals, linearize_extrapolation=linearize_extrapolation, device=device, dtype=dtype)
+        _setup.check_host_bounds(grids, spec, dtype, [np.ascontiguousarray(xi[..., d].ravel()) for d in range(nd)], bounds_atol)
+    fs = _setup.create(Fields, method, grids, spec, vals, dtype, device, linearize_extrapolation=linearize_extrapolation)
     try:
         if on_device:
-            if check_bounds:  # the bounds are the grid's: any one field's interpolator checks them on the device
-                from .handle import Interpolator
-
-                one = (Interpolator.regular(method, dims, starts, steps, vals[0], device=device, dtype=dtype) if regular
-                       else Interpolator.rectilinear(method, grids, vals[0], device=device, dtype=dtype))
-                try:
-                    cols = [xi[..., d].reshape(-1).contiguous() for d in range(nd)]
-                    if one.check_bounds_tensors(cols, bounds_atol).any():
-                        raise ValueError("Observation points violate interpolator bounds")
-                finally:
-                    one.close()
+            if check_bounds:
+                cols = [xi[..., d].reshape(-1).contiguous() for d in range(nd)]
+                _setup.check_field_device_bounds(method, grids, spec, vals, dtype, device, cols, bounds_atol)
             res = fs.eval_points_tensors(xi, out)
             fs.finish()
         else:
@@ -953,3 +736,4 @@ def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, lineari
     finally:
         fs.close()
     return res
+

@@ -14,7 +14,7 @@ from ctypes import POINTER, c_double, c_float, c_size_t, c_uint64, c_void_p
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
 from .raw import _check_arr, _dims, _slice_of_slices
 
 
@@ -196,24 +196,15 @@ class Interpolator:
         return None if v < 0 else (v >> 16, (v >> 8) & 0xFF, v & 0xFF)
 
     def _check_same_device(self, what: str, tensor) -> None:
-        """Kernels run under the handle's device with the grid resident there: a tensor on another
-        GPU would be read across devices on a stream of the wrong device."""
-        idx = tensor.device.index
-        if idx is None:
-            import torch
-
-            idx = torch.cuda.current_device()
-        if idx != self.device():
-            raise ValueError(f"{what} is on cuda:{idx} but this interpolator lives on cuda:{self.device()}")
+        """`_args.same_device` against this interpolator's GPU."""
+        _args.same_device(what, tensor, self.device(), "interpolator", True)
 
     def eval_host(self, obs, out: np.ndarray) -> np.ndarray:
         """`.interp(obs, out)` on host arrays (synchronous)."""
         lib = _lib.load()
         out = _check_arr("out", out, self.dtype, writable=True)
         optr, olen, nobs, _keep = _slice_of_slices("obs", obs, self.dtype)
-        vp = (c_void_p * max(nobs, 1))()
-        for i in range(nobs):
-            vp[i] = ctypes.cast(optr[i], c_void_p)
+        vp = _args.void_pp(optr)
         st = lib.interpn_hip_eval_host(self._h, vp, olen, nobs, out.ctypes.data_as(c_void_p), out.size)
         _lib.raise_for_status(st)
         return out
@@ -236,13 +227,11 @@ class Interpolator:
         Returns the path taken, "in_place", "binned" or "sweep" (also kept in `.last_path`, with
         `.last_path_reason` saying why a handle that can sort its points evaluated in place)."""
         lib = _lib.load()
-        n = len(obs_ptrs)
-        vp = (c_void_p * max(n, 1))()
-        for i, p in enumerate(obs_ptrs):
-            vp[i] = c_void_p(int(p))
+        vp = _args.ptr_array(int(p) for p in obs_ptrs)
         path, why = ctypes.c_int(0), ctypes.c_int(0)
-        st = lib.interpn_hip_eval_device_ex(self._h, vp, n, c_void_p(int(out_ptr)), int(npoints), c_void_p(int(stream)),
-                                            _lib.EVAL_NO_ALLOC if no_alloc else 0, ctypes.byref(path), ctypes.byref(why))
+        st = lib.interpn_hip_eval_device_ex(self._h, vp, len(obs_ptrs), c_void_p(int(out_ptr)), int(npoints),
+                                            c_void_p(int(stream)), _args.eval_flags(no_alloc), ctypes.byref(path),
+                                            ctypes.byref(why))
         _lib.raise_for_status(st)
         self.last_path = {_lib.PATH_BINNED: "binned", _lib.PATH_SWEEP: "sweep"}.get(path.value, "in_place")
         self.last_path_reason = _lib.WHY.get(why.value, str(why.value))
@@ -253,34 +242,23 @@ class Interpolator:
         """Evaluate on torch CUDA tensors (asynchronous on torch's current stream unless given: a
         torch Stream or a raw hipStream_t integer).  Call `finish()` to synchronise and surface
         "Unrepresentable coordinate value"."""
-        import torch
-
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        want = _args.torch_dtype(self.dtype)
         obs = list(obs)
-        for i, t in enumerate(obs):
-            if not (t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
-                raise TypeError(f"obs[{i}]: expected a contiguous 1-D {want} CUDA tensor")
-            self._check_same_device(f"obs[{i}]", t)
-        n = obs[0].numel() if obs else 0
-        for t in obs:
-            if t.numel() != n:
-                raise AssertionError("Dimension mismatch")
-        if out is None:
-            out = torch.empty(n, dtype=want, device=torch.device("cuda", self.device()))
-        elif not (out.is_cuda and out.is_contiguous() and out.dim() == 1 and out.dtype == want):
-            raise TypeError(f"out: expected a contiguous 1-D {want} CUDA tensor")
-        elif out.numel() != n:
-            raise AssertionError("Dimension mismatch")
-        else:
-            self._check_same_device("out", out)
-        owner = torch.cuda.current_stream(self.device()) if stream is None else stream
-        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        dev = self.device()
+        n = _args.coord_tensors("obs", obs, want, dev, "interpolator", True)
+        out = _args.out_tensor(out, n, want, dev)
+        raw, owner = _args.resolve_stream(stream, dev)
         self.eval_device_ptrs([t.data_ptr() for t in obs], out.data_ptr(), n, raw, no_alloc)
-        # keep the Stream OBJECT: a raw handle whose torch Stream was collected would dangle
-        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        self._pending_streams[raw] = owner
         return out
 
     # -- value and gradient (multilinear handles) --------------------------------------------
+    def _host_grad(self, grad, shape) -> None:
+        """What the host forms require of a caller's `grad` before they look at its strides."""
+        _args.check_ndarray("grad", grad, self.dtype)
+        if grad.shape != shape:
+            raise ValueError(f"grad: expected shape {shape}, got {grad.shape}")
+
     def eval_grad_host(self, obs, out: np.ndarray = None, grad: np.ndarray = None, _entry="interpn_hip_eval_grad_host"):
         """Value and gradient on host arrays (synchronous; `interpn_hip_eval_grad_host`): returns `(out, grad)` with
         `out[i]` the bits of `eval_host` and `grad[d, i]` the derivative of the interpolant with respect to coordinate d
@@ -294,21 +272,13 @@ class Interpolator:
         if grad is None:
             grad = np.zeros((nobs, n), dtype=self.dtype)
         out = _check_arr("out", out, self.dtype, writable=True)
-        if not isinstance(grad, np.ndarray):
-            raise TypeError(f"argument 'grad': expected a numpy array, got {type(grad).__name__}")
-        if grad.dtype != self.dtype:
-            raise TypeError(f"argument 'grad': expected dtype {self.dtype.name}, got {grad.dtype.name}")
-        if grad.shape != (nobs, out.size):
-            raise ValueError(f"grad: expected shape {(nobs, out.size)}, got {grad.shape}")
+        self._host_grad(grad, (nobs, out.size))
         if grad.size and grad.strides[-1] != grad.itemsize:
             raise ValueError("argument 'grad': every row must be contiguous")
         if not grad.flags.writeable:
             raise ValueError("argument 'grad': array is read-only")
-        vp = (c_void_p * max(nobs, 1))()
-        gp = (c_void_p * max(nobs, 1))()
-        for i in range(nobs):
-            vp[i] = ctypes.cast(optr[i], c_void_p)
-            gp[i] = c_void_p(grad[i].ctypes.data)
+        vp = _args.void_pp(optr)
+        gp = _args.ptr_array(grad[i].ctypes.data for i in range(nobs))
         st = getattr(lib, _entry)(self._h, vp, olen, nobs, out.ctypes.data_as(c_void_p), out.size, gp)
         _lib.raise_for_status(st)
         return out, grad
@@ -317,43 +287,28 @@ class Interpolator:
         """The same on torch CUDA tensors (`interpn_hip_eval_grad_device`): one kernel, asynchronous like `eval_tensors`
         and capturable into a graph; `grad` is a tensor of shape `(N, n)` whose rows are contiguous.  `finish()`
         synchronises and surfaces "Unrepresentable coordinate value"."""
-        import torch
-
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        want = _args.torch_dtype(self.dtype)
         obs = list(obs)
-        for i, t in enumerate(obs):
-            if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
-                raise TypeError(f"obs[{i}]: expected a contiguous 1-D {want} CUDA tensor")
-            self._check_same_device(f"obs[{i}]", t)
-        n = obs[0].numel() if obs else 0
-        for t in obs:
-            if t.numel() != n:
-                raise AssertionError("Dimension mismatch")
-        dev = torch.device("cuda", self.device())
-        if out is None:
-            out = torch.empty(n, dtype=want, device=dev)
-        elif not (out.is_cuda and out.is_contiguous() and out.dim() == 1 and out.dtype == want):
-            raise TypeError(f"out: expected a contiguous 1-D {want} CUDA tensor")
-        elif out.numel() != n:
-            raise AssertionError("Dimension mismatch")
-        else:
-            self._check_same_device("out", out)
+        dev = self.device()
+        n = _args.coord_tensors("obs", obs, want, dev, "interpolator", True)
+        out = _args.out_tensor(out, n, want, dev)
+        k = len(obs)
         if grad is None:
-            grad = torch.empty((len(obs), n), dtype=want, device=dev)
+            import torch
+
+            grad = torch.empty((k, n), dtype=want, device=torch.device("cuda", dev))
         elif not (grad.is_cuda and grad.dim() == 2 and grad.dtype == want and (grad.numel() == 0 or grad.stride(1) == 1)):
             raise TypeError(f"grad: expected a 2-D {want} CUDA tensor with contiguous rows")
-        elif tuple(grad.shape) != (len(obs), n):
-            raise ValueError(f"grad: expected shape {(len(obs), n)}, got {tuple(grad.shape)}")
+        elif tuple(grad.shape) != (k, n):
+            raise ValueError(f"grad: expected shape {(k, n)}, got {tuple(grad.shape)}")
         else:
-            self._check_same_device("grad", grad)
-        owner = torch.cuda.current_stream(self.device()) if stream is None else stream
-        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
-        k = len(obs)
-        vp = (c_void_p * max(k, 1))(*[t.data_ptr() for t in obs])
-        gp = (c_void_p * max(k, 1))(*[grad[d].data_ptr() for d in range(k)])
+            _args.same_device("grad", grad, dev, "interpolator", True)
+        raw, owner = _args.resolve_stream(stream, dev)
+        vp = _args.ptr_array(t.data_ptr() for t in obs)
+        gp = _args.ptr_array(grad[d].data_ptr() for d in range(k))
         st = getattr(_lib.load(), _entry)(self._h, vp, k, c_void_p(out.data_ptr()), gp, n, c_void_p(int(raw)))
         _lib.raise_for_status(st)
-        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        self._pending_streams[raw] = owner
         return out, grad
 
     # -- value and gradient (multicubic handles) ----------------------------------------------
@@ -377,35 +332,48 @@ class Interpolator:
         `no_alloc=True`.  The fused kernel (multilinear N = 2, 3) needs none."""
         _lib.raise_for_status(_lib.load().interpn_hip_reserve_points(self._h, int(npoints), int(nstreams)))
 
+    def _host_rows(self, name: str, a: np.ndarray) -> int:
+        """The row stride of a host `(n, N)` array, points or gradient."""
+        return _args.row_stride(name, a.shape[0], self._ndims, _args.elem_strides(a), ValueError,
+                                "argument '{name}': every row must be contiguous",
+                                "argument '{name}': the row stride must be a whole number of elements, at least {width}")
+
+    def _host_points(self, pts, out):
+        """`(n, row stride, out)` of the host point-major forms: `pts` checked, `out` checked or made."""
+        _args.check_ndarray("pts", pts, self.dtype)
+        if pts.ndim != 2:
+            raise TypeError(f"argument 'pts': expected a 2-D array of shape (n, {self._ndims}), got {pts.ndim} dimension(s)")
+        n, width = pts.shape
+        if width != self._ndims:
+            raise _args.dim_mismatch(True)
+        stride = self._host_rows("pts", pts)
+        if out is None:
+            out = np.zeros(n, dtype=self.dtype)
+        out = _check_arr("out", out, self.dtype, writable=True)
+        if out.size != n:
+            raise _args.dim_mismatch(True)
+        return n, stride, out
+
+    def _tensor_points(self, pts, out, want, dev: int):
+        """`(n, row stride, out)` of the device point-major forms: `pts` checked, `out` checked or made."""
+        nd = self._ndims
+        what = f"pts: expected a 2-D {want} CUDA tensor of shape (n, {nd}) with stride(1) == 1 and stride(0) >= {nd}"
+        if not (hasattr(pts, "is_cuda") and pts.is_cuda and pts.dim() == 2 and pts.dtype == want):
+            raise TypeError(what)
+        n, width = int(pts.shape[0]), int(pts.shape[1])
+        stride = _args.row_stride("pts", n, width, pts.stride(), TypeError, what, what)
+        if width != nd:
+            raise _args.dim_mismatch(True)
+        _args.same_device("pts", pts, dev, "interpolator", True)
+        return n, stride, _args.out_tensor(out, n, want, dev, via_lib=True)
+
     def eval_points_host(self, pts: np.ndarray, out: np.ndarray = None) -> np.ndarray:
         """`.interp` on a host array of shape `(n, N)` whose rows are points (synchronous; `interpn_hip_eval_points_host`):
         `out[i]` has the bits of `eval_host` on the columns `pts[:, d]`, which are never made.  Rows must be contiguous
         (`pts.strides[1] == itemsize`); the row stride may be any whole number of elements >= N, so `buf[:, :3]` of an
         `(n, 4)` array is taken as it is.  On "Unrepresentable coordinate value" exactly the results in front of the
         failing point have been written."""
-        if not isinstance(pts, np.ndarray):
-            raise TypeError(f"argument 'pts': expected a numpy array, got {type(pts).__name__}")
-        if pts.dtype != self.dtype:
-            raise TypeError(f"argument 'pts': expected dtype {self.dtype.name}, got {pts.dtype.name}")
-        if pts.ndim != 2:
-            raise TypeError(f"argument 'pts': expected a 2-D array of shape (n, {self._ndims}), got {pts.ndim} dimension(s)")
-        n, width = pts.shape
-        if width != self._ndims:
-            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
-        item = pts.itemsize
-        stride = self._ndims
-        if n > 1 or width > 1:
-            if width > 1 and pts.strides[1] != item:
-                raise ValueError("argument 'pts': every row must be contiguous")
-            if n > 1:
-                if pts.strides[0] % item or pts.strides[0] < self._ndims * item:
-                    raise ValueError(f"argument 'pts': the row stride must be a whole number of elements, at least {self._ndims}")
-                stride = pts.strides[0] // item
-        if out is None:
-            out = np.zeros(n, dtype=self.dtype)
-        out = _check_arr("out", out, self.dtype, writable=True)
-        if out.size != n:
-            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        n, stride, out = self._host_points(pts, out)
         st = _lib.load().interpn_hip_eval_points_host(self._h, c_void_p(pts.ctypes.data), stride, n, out.ctypes.data_as(c_void_p))
         _lib.raise_for_status(st)
         return out
@@ -415,36 +383,14 @@ class Interpolator:
         `(n, N)` tensor, or `buf[:, :N]` of a wider one — without `pts.T.contiguous()` (`interpn_hip_eval_points_device`).
         Asynchronous like `eval_tensors`; multilinear N = 2, 3 is one kernel and capturable.  `last_points_path()` says
         which path ran; `finish()` synchronises and surfaces "Unrepresentable coordinate value"."""
-        import torch
-
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        nd = self._ndims
-        what = f"pts: expected a 2-D {want} CUDA tensor of shape (n, {nd}) with stride(1) == 1 and stride(0) >= {nd}"
-        if not (hasattr(pts, "is_cuda") and pts.is_cuda and pts.dim() == 2 and pts.dtype == want):
-            raise TypeError(what)
-        n, width = int(pts.shape[0]), int(pts.shape[1])
-        if (width > 1 and pts.stride(1) != 1) or (n > 1 and pts.stride(0) < width):
-            raise TypeError(what)
-        if width != nd:
-            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
-        self._check_same_device("pts", pts)
-        stride = int(pts.stride(0)) if n > 1 else nd
-        if out is None:
-            out = torch.empty(n, dtype=want, device=torch.device("cuda", self.device()))
-        elif not (out.is_cuda and out.is_contiguous() and out.dim() == 1 and out.dtype == want):
-            raise TypeError(f"out: expected a contiguous 1-D {want} CUDA tensor")
-        elif out.numel() != n:
-            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
-        else:
-            self._check_same_device("out", out)
-        owner = torch.cuda.current_stream(self.device()) if stream is None else stream
-        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        dev = self.device()
+        n, stride, out = self._tensor_points(pts, out, _args.torch_dtype(self.dtype), dev)
+        raw, owner = _args.resolve_stream(stream, dev)
         path = ctypes.c_int(0)
         st = _lib.load().interpn_hip_eval_points_device(self._h, c_void_p(pts.data_ptr()), stride, n, c_void_p(out.data_ptr()),
-                                                        c_void_p(int(raw)), _lib.EVAL_NO_ALLOC if no_alloc else 0,
-                                                        ctypes.byref(path))
+                                                        c_void_p(int(raw)), _args.eval_flags(no_alloc), ctypes.byref(path))
         _lib.raise_for_status(st)
-        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        self._pending_streams[raw] = owner
         return out
 
     # -- point-major value and gradient (positions (n, N) in, gradient (n, N) out) -----------------
@@ -460,45 +406,13 @@ class Interpolator:
         `grad[i, d]` being the derivative with respect to coordinate d at point i.  `pts` as for `eval_points_host`; a
         caller's `grad` may be a row-strided view such as `g[:, :3]` of an `(n, 4)` array, whose other columns are left
         alone.  On "Unrepresentable coordinate value" exactly the entries in front of the failing point have been written."""
-        if not isinstance(pts, np.ndarray):
-            raise TypeError(f"argument 'pts': expected a numpy array, got {type(pts).__name__}")
-        if pts.dtype != self.dtype:
-            raise TypeError(f"argument 'pts': expected dtype {self.dtype.name}, got {pts.dtype.name}")
-        if pts.ndim != 2:
-            raise TypeError(f"argument 'pts': expected a 2-D array of shape (n, {self._ndims}), got {pts.ndim} dimension(s)")
-        n, width = pts.shape
-        if width != self._ndims:
-            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
-        item = pts.itemsize
-
-        def row_stride(name, a):
-            stride = self._ndims
-            if n > 1 or width > 1:
-                if width > 1 and a.strides[1] != item:
-                    raise ValueError(f"argument '{name}': every row must be contiguous")
-                if n > 1:
-                    if a.strides[0] % item or a.strides[0] < self._ndims * item:
-                        raise ValueError(f"argument '{name}': the row stride must be a whole number of elements, at least {self._ndims}")
-                    stride = a.strides[0] // item
-            return stride
-
-        stride = row_stride("pts", pts)
-        if out is None:
-            out = np.zeros(n, dtype=self.dtype)
-        out = _check_arr("out", out, self.dtype, writable=True)
-        if out.size != n:
-            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
+        n, stride, out = self._host_points(pts, out)
         if grad is None:
-            grad = np.zeros((n, width), dtype=self.dtype)
-        if not isinstance(grad, np.ndarray):
-            raise TypeError(f"argument 'grad': expected a numpy array, got {type(grad).__name__}")
-        if grad.dtype != self.dtype:
-            raise TypeError(f"argument 'grad': expected dtype {self.dtype.name}, got {grad.dtype.name}")
-        if grad.shape != (n, width):
-            raise ValueError(f"grad: expected shape {(n, width)}, got {grad.shape}")
+            grad = np.zeros((n, self._ndims), dtype=self.dtype)
+        self._host_grad(grad, (n, self._ndims))
         if not grad.flags.writeable:
             raise ValueError("argument 'grad': array is read-only")
-        gstride = row_stride("grad", grad)
+        gstride = self._host_rows("grad", grad)
         st = _lib.load().interpn_hip_eval_points_grad_host(self._h, c_void_p(pts.ctypes.data), stride, n, out.ctypes.data_as(c_void_p),
                                                            c_void_p(grad.ctypes.data), gstride)
         _lib.raise_for_status(st)
@@ -511,49 +425,28 @@ class Interpolator:
         `stride(0) >= N`) that does not overlap `pts`.  Asynchronous like `eval_tensors`; multilinear and multicubic
         N = 2, 3 are one kernel and capturable.  `last_points_path()` says which path ran; `finish()` synchronises and
         surfaces "Unrepresentable coordinate value"."""
-        import torch
-
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        want = _args.torch_dtype(self.dtype)
         nd = self._ndims
-        what = f"pts: expected a 2-D {want} CUDA tensor of shape (n, {nd}) with stride(1) == 1 and stride(0) >= {nd}"
-        if not (hasattr(pts, "is_cuda") and pts.is_cuda and pts.dim() == 2 and pts.dtype == want):
-            raise TypeError(what)
-        n, width = int(pts.shape[0]), int(pts.shape[1])
-        if (width > 1 and pts.stride(1) != 1) or (n > 1 and pts.stride(0) < width):
-            raise TypeError(what)
-        if width != nd:
-            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
-        self._check_same_device("pts", pts)
-        stride = int(pts.stride(0)) if n > 1 else nd
-        dev = torch.device("cuda", self.device())
-        if out is None:
-            out = torch.empty(n, dtype=want, device=dev)
-        elif not (out.is_cuda and out.is_contiguous() and out.dim() == 1 and out.dtype == want):
-            raise TypeError(f"out: expected a contiguous 1-D {want} CUDA tensor")
-        elif out.numel() != n:
-            raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
-        else:
-            self._check_same_device("out", out)
+        dev = self.device()
+        n, stride, out = self._tensor_points(pts, out, want, dev)
         gwhat = f"grad: expected a 2-D {want} CUDA tensor of shape ({n}, {nd}) with stride(1) == 1 and stride(0) >= {nd}"
         if grad is None:
-            grad = torch.empty((n, nd), dtype=want, device=dev)
+            import torch
+
+            grad = torch.empty((n, nd), dtype=want, device=torch.device("cuda", dev))
         elif not (hasattr(grad, "is_cuda") and grad.is_cuda and grad.dim() == 2 and grad.dtype == want):
             raise TypeError(gwhat)
         elif tuple(grad.shape) != (n, nd):
             raise ValueError(f"grad: expected shape {(n, nd)}, got {tuple(grad.shape)}")
-        elif (nd > 1 and grad.stride(1) != 1) or (n > 1 and grad.stride(0) < nd):
-            raise TypeError(gwhat)
-        else:
-            self._check_same_device("grad", grad)
-        gstride = int(grad.stride(0)) if n > 1 else nd
-        owner = torch.cuda.current_stream(self.device()) if stream is None else stream
-        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+        gstride = _args.row_stride("grad", n, nd, grad.stride(), TypeError, gwhat, gwhat)
+        _args.same_device("grad", grad, dev, "interpolator", True)
+        raw, owner = _args.resolve_stream(stream, dev)
         path = ctypes.c_int(0)
         st = _lib.load().interpn_hip_eval_points_grad_device(self._h, c_void_p(pts.data_ptr()), stride, n, c_void_p(out.data_ptr()),
                                                              c_void_p(grad.data_ptr()), gstride, c_void_p(int(raw)),
-                                                             _lib.EVAL_NO_ALLOC if no_alloc else 0, ctypes.byref(path))
+                                                             _args.eval_flags(no_alloc), ctypes.byref(path))
         _lib.raise_for_status(st)
-        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        self._pending_streams[raw] = owner
         return out, grad
 
     # -- lattice evaluation (points = tensor product of one coordinate vector per axis) ----
@@ -578,26 +471,17 @@ class Interpolator:
         shape = tuple(int(alen[i]) for i in range(naxes))
         if out is None:
             out = np.zeros(shape, dtype=self.dtype)
-        if not isinstance(out, np.ndarray):
-            raise TypeError(f"argument 'out': expected a numpy array, got {type(out).__name__}")
-        if out.dtype != self.dtype:
-            raise TypeError(f"argument 'out': expected dtype {self.dtype.name}, got {out.dtype.name}")
+        _args.check_ndarray("out", out, self.dtype)
         if naxes == self._ndims and out.shape != shape and out.shape != (int(np.prod(shape, dtype=object)),):
             raise ValueError(f"out: expected shape {shape}, got {out.shape}")
         if not out.flags.c_contiguous:
             raise ValueError("argument 'out': The given array is not contiguous")
         if not out.flags.writeable:
             raise ValueError("argument 'out': array is read-only")
-        vp = (c_void_p * max(naxes, 1))()
-        for i in range(naxes):
-            vp[i] = ctypes.cast(aptr[i], c_void_p)
+        vp = _args.void_pp(aptr)
         bad = c_uint64(0)
         st = lib.interpn_hip_eval_lattice_host(self._h, vp, alen, naxes, out.ctypes.data_as(c_void_p), ctypes.byref(bad))
-        if st in _lib.UNREPRESENTABLE:
-            err = AssertionError(_lib.strerror(st))
-            err.first_bad_index = bad.value
-            raise err
-        _lib.raise_for_status(st)
+        _args.raise_for_indexed_status(st, bad)
         return out
 
     def eval_lattice_tensors(self, axes, out=None, stream=None, no_alloc: bool = False):
@@ -605,60 +489,44 @@ class Interpolator:
         shape `tuple(len(a) for a in axes)`.  Asynchronous like `eval_tensors`; `finish()` synchronises and raises
         for a coordinate the reference cannot evaluate, with `first_bad_index` in C order.  `.last_lattice_path` says
         which path ran (`interpn_hip_eval_lattice_device`)."""
-        import torch
-
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        want = _args.torch_dtype(self.dtype)
         axes = list(axes)
-        for i, t in enumerate(axes):
-            if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
-                raise TypeError(f"axes[{i}]: expected a contiguous 1-D {want} CUDA tensor")
-            self._check_same_device(f"axes[{i}]", t)
+        dev = self.device()
+        _args.coord_tensors("axes", axes, want, dev, "interpolator", True, same_length=False)
         shape = tuple(int(t.numel()) for t in axes)
         count = int(np.prod(shape, dtype=object)) if shape else 0
         if out is None:
-            out = torch.empty(shape, dtype=want, device=torch.device("cuda", self.device()))
+            import torch
+
+            out = torch.empty(shape, dtype=want, device=torch.device("cuda", dev))
         elif not (out.is_cuda and out.is_contiguous() and out.dtype == want):
             raise TypeError(f"out: expected a contiguous {want} CUDA tensor")
         elif len(axes) == self._ndims and tuple(out.shape) != shape and tuple(out.shape) != (count,):
             raise ValueError(f"out: expected shape {shape}, got {tuple(out.shape)}")
         else:
-            self._check_same_device("out", out)
-        owner = torch.cuda.current_stream(self.device()) if stream is None else stream
-        raw = owner.cuda_stream if hasattr(owner, "cuda_stream") else int(owner)
+            _args.same_device("out", out, dev, "interpolator", True)
+        raw, owner = _args.resolve_stream(stream, dev)
         n = len(axes)
-        vp = (c_void_p * max(n, 1))(*[t.data_ptr() for t in axes])
         lens = (c_size_t * max(n, 1))(*shape)
         path = ctypes.c_int(0)
-        st = _lib.load().interpn_hip_eval_lattice_device(self._h, vp, lens, n, c_void_p(out.data_ptr()), c_void_p(int(raw)),
-                                                         _lib.EVAL_NO_ALLOC if no_alloc else 0, ctypes.byref(path))
+        st = _lib.load().interpn_hip_eval_lattice_device(self._h, _args.ptr_array(t.data_ptr() for t in axes), lens, n,
+                                                         c_void_p(out.data_ptr()), c_void_p(int(raw)), _args.eval_flags(no_alloc),
+                                                         ctypes.byref(path))
         _lib.raise_for_status(st)
-        self._pending_streams[raw] = owner if hasattr(owner, "cuda_stream") else None
+        self._pending_streams[raw] = owner
         return out
 
     def check_bounds_tensors(self, obs, atol: float, stream=None) -> np.ndarray:
         """`check_bounds` on torch CUDA tensors against this interpolator's grid: one flag per
         dimension, True where any coordinate lies outside the grid by `atol` or more
         (src/multilinear/regular.rs:145-182).  The points stay on the device."""
-        import torch
-
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
         obs = list(obs)
-        for i, t in enumerate(obs):
-            if not (t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.dtype == want):
-                raise TypeError(f"obs[{i}]: expected a contiguous 1-D {want} CUDA tensor")
-            self._check_same_device(f"obs[{i}]", t)
-        n = obs[0].numel() if obs else 0
-        for t in obs:
-            if t.numel() != n:
-                raise AssertionError(_lib.strerror(_lib.ERR_DIM_MISMATCH))
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device()).cuda_stream
-        vp = (c_void_p * max(len(obs), 1))()
-        for i, t in enumerate(obs):
-            vp[i] = c_void_p(t.data_ptr())
+        dev = self.device()
+        n = _args.coord_tensors("obs", obs, _args.torch_dtype(self.dtype), dev, "interpolator", True, via_lib=True)
+        raw = _args.resolve_stream(None, dev)[0] if stream is None else int(stream)
         flags = (ctypes.c_uint8 * max(len(obs), 1))()
-        st = _lib.load().interpn_hip_check_bounds_device(self._h, vp, len(obs), n, float(atol), flags, len(obs),
-                                                         c_void_p(int(stream)))
+        st = _lib.load().interpn_hip_check_bounds_device(self._h, _args.ptr_array(t.data_ptr() for t in obs), len(obs), n,
+                                                         float(atol), flags, len(obs), c_void_p(int(raw)))
         _lib.raise_for_status(st)
         return np.array([bool(flags[i]) for i in range(len(obs))])
 
@@ -670,7 +538,7 @@ class Interpolator:
         integer) only that one."""
         lib = _lib.load()
         if stream is not None:
-            raws = [stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)]
+            raws = [_args.resolve_stream(stream, None)[0]]
         else:
             raws = list(self._pending_streams)
         if not raws:
@@ -680,23 +548,7 @@ class Interpolator:
                 raws = [torch.cuda.current_stream(self.device()).cuda_stream if torch.cuda.is_available() else 0]
             except ImportError:
                 raws = [0]
-        first_bad = None
-        first_bad_status = _lib.ERR_UNREPRESENTABLE
-        status = _lib.OK
-        for raw in raws:
-            bad = c_uint64(0)
-            st = lib.interpn_hip_finish(self._h, c_void_p(int(raw)), ctypes.byref(bad))
-            self._pending_streams.pop(raw, None)
-            if st in _lib.UNREPRESENTABLE:
-                first_bad_status = st
-                first_bad = bad.value if first_bad is None else min(first_bad, bad.value)
-            elif st != _lib.OK and status == _lib.OK:
-                status = st
-        _lib.raise_for_status(status)
-        if first_bad is not None:
-            err = AssertionError(_lib.strerror(first_bad_status))
-            err.first_bad_index = first_bad
-            raise err
+        _args.finish_streams(lib.interpn_hip_finish, self._h, raws, self._pending_streams)
 
     def close(self) -> None:
         if self._h is not None and self._h.value:
@@ -722,20 +574,14 @@ def eval_host_sharded(interps, obs, out: np.ndarray) -> np.ndarray:
     dtype = interps[0].dtype
     out = _check_arr("out", out, dtype, writable=True)
     optr, olen, nobs, _keep = _slice_of_slices("obs", obs, dtype)
-    vp = (c_void_p * max(nobs, 1))()
-    for i in range(nobs):
-        vp[i] = ctypes.cast(optr[i], c_void_p)
+    vp = _args.void_pp(optr)
     hs = (c_void_p * len(interps))()
     for i, it in enumerate(interps):
         hs[i] = it._h
     bad = c_uint64(0)
     st = lib.interpn_hip_eval_host_sharded(hs, len(interps), vp, olen, nobs, out.ctypes.data_as(c_void_p), out.size,
                                            ctypes.byref(bad))
-    if st in _lib.UNREPRESENTABLE:
-        err = AssertionError(_lib.strerror(st))
-        err.first_bad_index = bad.value
-        raise err
-    _lib.raise_for_status(st)
+    _args.raise_for_indexed_status(st, bad)
     return out
 
 
@@ -754,7 +600,7 @@ def eval_device_sharded(interps, obs_shards, out_shards=None):
     lib = _lib.load()
     n = len(interps)
     nd = interps[0].ndims()
-    tdt = torch.float64 if interps[0].dtype == np.float64 else torch.float32
+    tdt = _args.torch_dtype(interps[0].dtype)
     outs = list(out_shards) if out_shards is not None else [None] * n
     hs = (c_void_p * n)()
     obs_pp = (ctypes.POINTER(c_void_p) * n)()
@@ -774,7 +620,7 @@ def eval_device_sharded(interps, obs_shards, out_shards=None):
         if outs[r] is None:
             outs[r] = torch.empty(count, dtype=tdt, device=shard[0].device)
         it._check_same_device("out", outs[r])
-        arr = (c_void_p * max(nd, 1))(*[t.data_ptr() for t in shard])
+        arr = _args.ptr_array(t.data_ptr() for t in shard)
         keep.append(arr)
         hs[r] = it._h
         obs_pp[r] = ctypes.cast(arr, ctypes.POINTER(c_void_p))
@@ -783,9 +629,6 @@ def eval_device_sharded(interps, obs_shards, out_shards=None):
         streams[r] = torch.cuda.current_stream(shard[0].device).cuda_stream
     bad = c_uint64(0)
     st = lib.interpn_hip_eval_device_sharded(hs, n, obs_pp, nd, out_p, npts, streams, ctypes.byref(bad))
-    if st in _lib.UNREPRESENTABLE:
-        err = AssertionError(_lib.strerror(st))
-        err.first_bad_index = bad.value
-        raise err
-    _lib.raise_for_status(st)
+    _args.raise_for_indexed_status(st, bad)
     return outs
+

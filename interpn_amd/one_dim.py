@@ -19,7 +19,7 @@ from ctypes import c_uint64, c_void_p
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
 from .handle import Interpolator
 from .raw import _check_arr
 
@@ -91,11 +91,7 @@ class _Interp1D:
             # the one-handle sharded form: the host path's abort-at-first-bad-point contract plus the failing index
             st = lib.interpn_hip_eval_host_sharded(hs, 1, vp, lens, 1, out.ctypes.data_as(c_void_p), out.shape[0],
                                                    ctypes.byref(bad))
-            if st in _lib.UNREPRESENTABLE:
-                err = AssertionError(_lib.strerror(st))
-                err.first_bad_index = bad.value
-                raise err
-            _lib.raise_for_status(st)
+            _args.raise_for_indexed_status(st, bad)
             return out
         if out is not None and int(out.numel()) != int(locs.numel()):
             raise AssertionError("Length mismatch")
