@@ -744,6 +744,51 @@ int interpn_hip_lattice_plan(size_t elem_size, int method, size_t ndims, const s
                              int* path, size_t* lds_bytes, size_t* npoints);
 
 /* ------------------------------------------------------------------------------------------
+ * Gradients on a lattice — the value and d/dx of every lattice point in one pass: forces from a potential table on a
+ * finer mesh, shading normals of a resampled volume, the partial derivatives of a refined equation-of-state table.
+ * `axes`, `axis_lens`, `naxes` as for interpn_hip_eval_lattice_device; `grad`: HOST array of `naxes` pointers to
+ * prod(axis_lens) elements each, as in interpn_hip_eval_grad_device; grad[d][p] is the derivative with respect to
+ * coordinate d at the lattice point p (C order).
+ *
+ * Contract  nothing new is defined: out[p] has the bits of interpn_hip_eval_lattice_device, and grad[d][p] the bits of
+ *           component d of interpn_hip_eval_grad_device (multilinear handles) or interpn_hip_eval_cubic_grad_device
+ *           (multicubic handles) on the expanded point, in both fma flavours.  Nearest and interpn::one_dim handles:
+ *           INTERPN_HIP_ERR_UNSUPPORTED before any device work, as for those entry points.
+ * Paths     FUSED (the coverage of interpn_hip_eval_lattice_device's fused path): the unchanged interpn::k_lattice_axes
+ *           launch, then interpn::k_lattice_grad_rows, in which a wave owns L lines instead of one — multilinear L =
+ *           N + 1 (the value, one per component d < N-1, and the differences along the last axis, which the definition
+ *           takes before it reduces), multicubic L = N (the value and one per component d < N-1; the last component is
+ *           the derivative node of the value line).  A wave's lines lie packed: the condition is
+ *           4 * round16(L * n_{N-1} * sizeof(T)) within the budget "axis_lds_kb".  Per point it moves (N + 1) sizeof(T)
+ *           bytes instead of (2 N + 1) sizeof(T).
+ *           EXPANDED (everything else): the expanded path of interpn_hip_eval_lattice_device, each slice through
+ *           interpn_hip_eval_grad_device / interpn_hip_eval_cubic_grad_device.
+ * Options   "lattice" governs value and gradient calls alike; automatic mode applies the value path's two rules (carried
+ *           over; the measured rows ask for no tighter ones: DESIGN.md section 18).  "last_lattice_path" and *path_taken as for the
+ *           value; interpn_hip_kernel_name reports "interpn::k_lattice_grad_rows<T, method, N, rectilinear, fma>" after a
+ *           fused call.
+ * Scratch   exactly the value call's (records when fused; flags and one coordinate slice when expanded), under the same
+ *           rules, graph capture included.  interpn_hip_reserve_lattice serves gradient calls: there is no separate
+ *           reserve entry point.
+ * Checks    those of interpn_hip_eval_lattice_device in their order; then a handle that is neither multilinear nor
+ *           multicubic: INTERPN_HIP_ERR_UNSUPPORTED; then `grad` or a grad[d] NULL: INTERPN_HIP_ERR_INVALID_ARGUMENT.  An
+ *           empty axis: INTERPN_HIP_OK, nothing written.
+ * Failing   as for the value call: the same first index in C order through interpn_hip_finish.
+ * points
+ * ---------------------------------------------------------------------------------------- */
+int interpn_hip_eval_lattice_grad_device(interpn_hip_interp* h, const void* const* axes, const size_t* axis_lens, size_t naxes,
+                                         void* out, void* const* grad, void* stream, unsigned flags, int* path_taken);
+/* The same on host arrays, synchronous (chunks of leading-axis indices, about 2^25 / (N + 1) points each; option
+ * "host_chunk": points).  On a failing point the status is the handle's, exactly out[0..first_bad) and
+ * grad[d][0..first_bad) are written, the rest is left as it was, and *first_bad_index (may be NULL) receives the index. */
+int interpn_hip_eval_lattice_grad_host(interpn_hip_interp* h, const void* const* axes, const size_t* axis_lens, size_t naxes,
+                                       void* out, void* const* grad, uint64_t* first_bad_index);
+/* interpn_hip_lattice_plan for a value-and-gradient call (no device; the same environment latches and statuses), except
+ * that the nearest method has no gradient: INTERPN_HIP_ERR_UNSUPPORTED. */
+int interpn_hip_lattice_grad_plan(size_t elem_size, int method, size_t ndims, const size_t* dims, const size_t* axis_lens,
+                                  int* path, size_t* lds_bytes, size_t* npoints);
+
+/* ------------------------------------------------------------------------------------------
  * Field sets on a lattice — K fields of one grid re-gridded onto the tensor product of N coordinate vectors in one pass:
  * resizing an (H, W, C) image or a (D, H, W, C) volume, re-gridding several variables of a simulation onto a finer mesh,
  * refining a table of K quantities.  `axes`, `axis_lens`, `naxes` as for interpn_hip_eval_lattice_device.

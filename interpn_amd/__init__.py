@@ -50,7 +50,9 @@ __all__ = [
     "interpn_lattice",
     "interpn_points",
     "interpn_points_grad",
+    "interpn_lattice_grad",
     "lattice_plan",
+    "lattice_grad_plan",
     "Fields",
     "fields_lattice_plan",
     "fields_layout",
@@ -335,6 +337,11 @@ def interpn_lattice(
     The rules are those of `interpn()`: inputs ravelled, dtype from `vals`, regular iff every spacing is exactly equal or
     `assume_regular`.  `check_bounds` checks the N vectors (a lattice is inside the grid exactly when each axis is)."""
     _setup.check_method(method)
+    return _lattice_call(axes, grids, vals, method, out, linearize_extrapolation, assume_regular, check_bounds, bounds_atol, False)
+
+
+def _lattice_call(axes, grids, vals, method, out, linearize_extrapolation, assume_regular, check_bounds, bounds_atol, with_grad):
+    """What `interpn_lattice` and `interpn_lattice_grad` share: set-up, the bounds check on the N vectors, the evaluation."""
     axes, grids = list(axes), list(grids)
     if len(axes) != len(grids):
         raise ValueError(f"axes: expected {len(grids)} coordinate vectors (one per grid axis), got {len(axes)}")
@@ -362,19 +369,52 @@ def interpn_lattice(
                 if it.check_bounds_tensors(batch, bounds_atol)[d]:
                     raise ValueError(_setup.OUT_OF_BOUNDS)
         if on_device:
-            res = it.eval_lattice_tensors(axes, out)
+            res = it.eval_lattice_grad_tensors(axes, out) if with_grad else it.eval_lattice_tensors(axes, out)
             it.finish()
         else:
-            res = it.eval_lattice_host(axes, out)
+            res = it.eval_lattice_grad_host(axes, out) if with_grad else it.eval_lattice_host(axes, out)
     finally:
         it.close()
     return res
+
+
+def interpn_lattice_grad(
+    axes: Sequence,
+    grids: Sequence,
+    vals,
+    *,
+    method: str = "linear",
+    out=None,
+    linearize_extrapolation: bool = True,
+    assume_regular: bool = False,
+    check_bounds: bool = False,
+    bounds_atol: float = 1e-8,
+):
+    """`interpn_grad()` on the lattice axes[0] x .. x axes[N-1]: returns `(out, grad)` of shapes `(*m)` and `(N, *m)`, m =
+    the vectors' lengths — arrays for numpy vectors, tensors for torch CUDA ones — with the bits of
+    `interpn_grad(np.meshgrid(*axes, indexing="ij"), grids, vals, ...)`, without the meshgrid: forces on a finer mesh, the
+    partial derivatives of a refined table.  `method` "linear" or "cubic"; `linearize_extrapolation` has no effect on the
+    linear method; the other rules are those of `interpn_lattice()`."""
+    if method not in ("linear", "cubic"):
+        raise ValueError(f"interpn_lattice_grad: method must be \"linear\" or \"cubic\", got {method!r}")
+    lin = bool(linearize_extrapolation) if method == "cubic" else False
+    return _lattice_call(axes, grids, vals, method, out, lin, assume_regular, check_bounds, bounds_atol, True)
 
 
 def lattice_plan(dtype, method: str, dims, axis_lens):
     """(path, lds_bytes, npoints): the path ("fused" / "expanded") a lattice of `axis_lens` coordinates per axis takes in
     automatic mode on a grid of `dims`, the LDS bytes of the fused kernel's workgroup and the point count
     (`interpn_hip_lattice_plan`; needs no device)."""
+    return _lattice_plan("interpn_hip_lattice_plan", dtype, method, dims, axis_lens)
+
+
+def lattice_grad_plan(dtype, method: str, dims, axis_lens):
+    """`lattice_plan` for a value-and-gradient call (`interpn_hip_lattice_grad_plan`; needs no device): the fused kernel
+    keeps L lines per wave (multilinear N + 1, multicubic N) where the value's keeps one.  `method` "linear" or "cubic"."""
+    return _lattice_plan("interpn_hip_lattice_grad_plan", dtype, method, dims, axis_lens)
+
+
+def _lattice_plan(entry, dtype, method, dims, axis_lens):
     import ctypes
 
     from .raw import _dims
@@ -384,8 +424,8 @@ def lattice_plan(dtype, method: str, dims, axis_lens):
     if nd != nm:
         raise ValueError(f"axis_lens: expected {nd} lengths, got {nm}")
     path, lds, npts = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
-    st = _lib.load().interpn_hip_lattice_plan(np.dtype(dtype).itemsize, _lib.METHODS[method], nd, d, m, ctypes.byref(path),
-                                              ctypes.byref(lds), ctypes.byref(npts))
+    st = getattr(_lib.load(), entry)(np.dtype(dtype).itemsize, _lib.METHODS[method], nd, d, m, ctypes.byref(path),
+                                     ctypes.byref(lds), ctypes.byref(npts))
     _lib.raise_for_status(st)
     return _lib.LATTICE_PATHS[path.value], int(lds.value), int(npts.value)
 

@@ -12,6 +12,10 @@ graph: the gradient with respect to `vals` is not built.
 `interp_fields(fs, obs)` is `interp` for a field set (`Fields`): a `(K, *shape)` tensor whose forward pass is one
 `Fields.eval_grad_tensors`; the saved Jacobian turns the incoming `(K, *shape)` gradient into one gradient per coordinate.
 
+`interp_lattice(it, axes)` is `interp` on the lattice axes[0] x .. x axes[N-1]: its forward pass is one
+`Interpolator.eval_lattice_grad_tensors`; the backward pass sums the incoming `(*m)` gradient times component d over every
+lattice dimension but d, which gives one gradient per coordinate VECTOR.
+
 torch is imported on first use, and this module is not imported by `import interpn_amd`.
 """
 
@@ -20,6 +24,7 @@ from __future__ import annotations
 _FUNCTION = None
 _POINTS_FUNCTION = None
 _FIELDS_FUNCTION = None
+_LATTICE_FUNCTION = None
 
 
 def _function():
@@ -132,3 +137,45 @@ def interp_fields(fs, obs):
     tensors of the set's dtype): a tensor of shape `(K, *obs[0].shape)`, differentiable with respect to every tensor of `obs`.
     The table stays a constant of the graph."""
     return _fields_function().apply(fs, *obs)
+
+
+def _lattice_function():
+    """The lattice torch.autograd.Function, built on first use like `_function`."""
+    global _LATTICE_FUNCTION
+    if _LATTICE_FUNCTION is not None:
+        return _LATTICE_FUNCTION
+    import torch
+
+    class _InterpLattice(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, it, *axes):
+            flat = [a.detach().reshape(-1).contiguous() for a in axes]
+            out, grad = it.eval_lattice_grad_tensors(flat)
+            it.finish()
+            ctx.save_for_backward(grad)
+            ctx.axis_shapes = [a.shape for a in axes]
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            (grad,) = ctx.saved_tensors  # (N, *m)
+            n = grad.shape[0]
+            res = [None]
+            for d in range(n):
+                if not ctx.needs_input_grad[d + 1]:
+                    res.append(None)
+                    continue
+                full = grad_out * grad[d]
+                others = [e for e in range(n) if e != d]
+                res.append((full.sum(dim=others) if others else full).reshape(ctx.axis_shapes[d]))
+            return tuple(res)
+
+    _LATTICE_FUNCTION = _InterpLattice
+    return _LATTICE_FUNCTION
+
+
+def interp_lattice(it, axes):
+    """Value of the multilinear or multicubic interpolator `it` on the lattice axes[0] x .. x axes[N-1] (a sequence of N torch
+    CUDA coordinate vectors of the handle's dtype): a tensor of shape `tuple(len(a) for a in axes)`, differentiable with
+    respect to every vector of `axes`."""
+    return _lattice_function().apply(it, *axes)

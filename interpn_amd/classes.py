@@ -91,6 +91,17 @@ class _Base:
             raise TypeError(f"Unexpected data type: {dtype}")
         return self._interp().eval_lattice_host([np.ascontiguousarray(np.asarray(a).ravel()) for a in axes], out)
 
+    def _eval_lattice_grad(self, axes, out=None, grad=None):
+        axes = list(axes)
+        if axes and _is_tensor(axes[0]):
+            res = self._interp().eval_lattice_grad_tensors([a.reshape(-1).contiguous() for a in axes], out, grad)
+            self._interp().finish()
+            return res
+        dtype = self.vals.dtype
+        if dtype not in (np.float64, np.float32):
+            raise TypeError(f"Unexpected data type: {dtype}")
+        return self._interp().eval_lattice_grad_host([np.ascontiguousarray(np.asarray(a).ravel()) for a in axes], out, grad)
+
     def eval_grad(self, obs, out=None, grad=None, _cubic=False):
         """Value and gradient at observation points (numpy arrays or torch CUDA tensors like `eval`): returns
         `(out, grad)`, `out` with the bits of `eval` and `grad[d]` the derivative of the interpolant with respect to
@@ -316,6 +327,13 @@ class MultilinearRegular(_RegularBase):
 
     _method = "linear"
 
+    def eval_lattice_grad(self, axes, out=None, grad=None):
+        """Value and gradient on the lattice axes[0] x .. x axes[N-1] (numpy arrays or torch CUDA tensors like
+        `eval_lattice`): returns `(out, grad)` of shapes `(*m)` and `(N, *m)`, `out` with the bits of `eval_lattice` and
+        `grad[d]` those of component d of `eval_grad` on the `meshgrid(..., indexing="ij")` of the vectors, which is never
+        materialised."""
+        return self._eval_lattice_grad(axes, out, grad)
+
     def eval_points_grad(self, pts, out=None, grad=None):
         """Value and gradient at points given as ONE array of shape `(..., N)` (numpy, or a torch CUDA tensor like `eval`):
         returns `(out, grad)` of shapes `pts.shape[:-1]` and `pts.shape`, `grad[..., d]` the derivative with respect to
@@ -333,6 +351,13 @@ class MultilinearRectilinear(_RectilinearBase):
     """Multilinear interpolation on a rectilinear grid (src/interpn/multilinear_rectilinear.py:24)."""
 
     _method = "linear"
+
+    def eval_lattice_grad(self, axes, out=None, grad=None):
+        """Value and gradient on the lattice axes[0] x .. x axes[N-1] (numpy arrays or torch CUDA tensors like
+        `eval_lattice`): returns `(out, grad)` of shapes `(*m)` and `(N, *m)`, `out` with the bits of `eval_lattice` and
+        `grad[d]` those of component d of `eval_grad` on the `meshgrid(..., indexing="ij")` of the vectors, which is never
+        materialised."""
+        return self._eval_lattice_grad(axes, out, grad)
 
     def eval_points_grad(self, pts, out=None, grad=None):
         """Value and gradient at points given as ONE array of shape `(..., N)` (numpy, or a torch CUDA tensor like `eval`):
@@ -394,6 +419,13 @@ class MulticubicRegular(_RegularBase):
         of the Hermite piece the value uses with respect to coordinate d (DESIGN.md "Multicubic gradients")."""
         return self.eval_grad(obs, out, grad, _cubic=True)
 
+    def eval_lattice_grad(self, axes, out=None, grad=None):
+        """Value and gradient on the lattice axes[0] x .. x axes[N-1] (numpy arrays or torch CUDA tensors like
+        `eval_lattice`): returns `(out, grad)` of shapes `(*m)` and `(N, *m)`, `out` with the bits of `eval_lattice` and
+        `grad[d]` those of component d of `eval_cubic_grad` on the `meshgrid(..., indexing="ij")` of the vectors, which is never
+        materialised."""
+        return self._eval_lattice_grad(axes, out, grad)
+
     def eval_points_grad(self, pts, out=None, grad=None):
         """Value and gradient at points given as ONE array of shape `(..., N)` (numpy, or a torch CUDA tensor like `eval`):
         returns `(out, grad)` of shapes `pts.shape[:-1]` and `pts.shape`, `grad[..., d]` the derivative with respect to
@@ -420,6 +452,13 @@ class MulticubicRectilinear(_RectilinearBase):
         """Value and gradient at observation points, like the multilinear classes' `eval_grad`: `grad[d]` is the derivative
         of the Hermite piece the value uses with respect to coordinate d (DESIGN.md "Multicubic gradients")."""
         return self.eval_grad(obs, out, grad, _cubic=True)
+
+    def eval_lattice_grad(self, axes, out=None, grad=None):
+        """Value and gradient on the lattice axes[0] x .. x axes[N-1] (numpy arrays or torch CUDA tensors like
+        `eval_lattice`): returns `(out, grad)` of shapes `(*m)` and `(N, *m)`, `out` with the bits of `eval_lattice` and
+        `grad[d]` those of component d of `eval_cubic_grad` on the `meshgrid(..., indexing="ij")` of the vectors, which is never
+        materialised."""
+        return self._eval_lattice_grad(axes, out, grad)
 
     def eval_points_grad(self, pts, out=None, grad=None):
         """Value and gradient at points given as ONE array of shape `(..., N)` (numpy, or a torch CUDA tensor like `eval`):

@@ -14,6 +14,7 @@
 //   abi_fields.hip    field sets: creation, column and point-major forms, options
 //   abi_fields_grad.hip  values and Jacobian of a field set (fields_eval_grad_device / _host)
 //   abi_fields_lattice.hip  field sets on a lattice (fields_eval_lattice_device / _host, fields_reserve_lattice, fields_lattice_plan)
+//   abi_lattice_grad.hip  value and gradient on a lattice (eval_lattice_grad_device / _host, lattice_grad_plan)
 //   scratch_slots.h   (no HIP in it) scratch blocks between streams and stream marks: settle / take / release / reserve /
 //                     mark / the wait at destroy, against a runtime type; HipRuntime below is the product's
 //   abi_points.hip    point-major observation points (eval_points_device / _host, reserve_points) and their gradient form
@@ -428,6 +429,7 @@ int validate_lattice(const interpn_hip_interp* h, const void* const* axes, const
 interpn::LatticePlan lattice_plan_for(const GridDesc& g, const interpn::LatticeShape& s);
 size_t lattice_scratch_need(const GridDesc& g, const interpn::LatticeShape& s, const interpn::LatticePlan& p);
 size_t lattice_reserve_need(const GridDesc& g, const interpn::LatticeShape& s);
+size_t lattice_expand_slice(const GridDesc& g, size_t npoints);
 int lattice_device(interpn_hip_interp* h, const interpn::LatticeShape& s, void* out, hipStream_t stream, unsigned flags, int* path_taken);
 constexpr size_t kExpandSliceBytes = (size_t)64 << 20;  // coordinates of one slice (bounds the scratch block)
 constexpr size_t kExpandSliceMin = (size_t)1 << 16;     // ... but never fewer points than this

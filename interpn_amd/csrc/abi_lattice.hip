@@ -73,7 +73,8 @@ LatticePlan lattice_plan_for(const GridDesc& g, const LatticeShape& s) {
   return lattice_plan(g.method, g.ndims, g.dtype == kF64 ? 8 : 4, g.n, s.m, lattice_lds_budget(g.cfg), g.cfg.num_cus, g.cfg.lattice);
 }
 
-static size_t expand_slice(const GridDesc& g, size_t npoints) {
+// Points per slice of the expanded path.
+size_t lattice_expand_slice(const GridDesc& g, size_t npoints) {
   const size_t elem = g.dtype == kF64 ? 8 : 4;
   size_t slice = kExpandSliceBytes / ((size_t)g.ndims * elem);
   if (slice < kExpandSliceMin) slice = kExpandSliceMin;
@@ -86,7 +87,7 @@ size_t lattice_scratch_need(const GridDesc& g, const LatticeShape& s, const Latt
   const size_t elem = g.dtype == kF64 ? 8 : 4;
   if (p.fused) return align_up(s.coords * lattice_record_bytes(g.method, g.kind, elem), 256);
   const size_t flags = g.kind == kRegular ? align_up(s.coords, 256) : 0;
-  return flags + (size_t)g.ndims * align_up(expand_slice(g, s.npoints) * elem, 256);
+  return flags + (size_t)g.ndims * align_up(lattice_expand_slice(g, s.npoints) * elem, 256);
 }
 
 // One lattice on device arrays.  Arguments are validated; the current device is the handle's.
@@ -113,7 +114,7 @@ int lattice_device(interpn_hip_interp* h, const LatticeShape& s, void* out, hipS
   } else {
     unsigned char* bad = g.kind == kRegular ? scratch : nullptr;
     const size_t flags_bytes = bad ? align_up(s.coords, 256) : 0;
-    const size_t slice = expand_slice(g, s.npoints);
+    const size_t slice = lattice_expand_slice(g, s.npoints);
     const size_t pitch = align_up(slice * elem, 256);
     void* dst[8] = {nullptr};
     for (int d = 0; d < g.ndims; ++d) dst[d] = scratch + flags_bytes + (size_t)d * pitch;

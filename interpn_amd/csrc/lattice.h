@@ -83,6 +83,40 @@ inline LatticePlan lattice_plan(int method, int ndims, size_t elem, const int* n
   return p;
 }
 
+// ---- Gradients on a lattice (lattice_grad.h, k_lattice_grad.hip) ---------------------------------------------------------
+// A wave of k_lattice_grad_rows owns L lines where k_lattice_rows owns one: the value line and one line per gradient
+// component (multilinear: N + 1, the last component's differences along the last axis being a line of their own;
+// multicubic: N, the last component coming from the value line's derivative node).
+inline int lattice_grad_lines(int method, int ndims) { return method == kLinear ? ndims + 1 : ndims; }
+// The L lines of a wave lie packed, n_{N-1} elements each (a line needs its element's alignment only); the wave's part is
+// rounded up to 16 bytes.  3-D f64 in 20 KiB: multilinear n_last <= 160 (4 waves x 4 lines x 1280 bytes), multicubic <= 213.
+inline size_t lattice_grad_wave_bytes(int lines, size_t n_last, size_t elem) {
+  return ((size_t)lines * n_last * elem + 15) & ~(size_t)15;
+}
+
+// Which path a value-and-gradient call takes on a lattice: lattice_plan's coverage, mode and automatic rules (carried
+// over from the value kernel), `fits` for the L lines of a wave.
+inline LatticePlan lattice_grad_plan(int method, int ndims, size_t elem, const int* n, const size_t* m, size_t budget, int num_cus,
+                                     int mode) {
+  LatticePlan p;
+  p.covered = (method == kLinear || method == kCubic) && (ndims == 2 || ndims == 3);
+  if (!p.covered) return p;
+  const size_t n_last = (size_t)n[ndims - 1], m_last = m[ndims - 1];
+  const size_t lds = (size_t)kLatticeWaves * lattice_grad_wave_bytes(lattice_grad_lines(method, ndims), n_last, elem);
+  p.fits = lds <= budget;
+  p.nrows = 1;
+  for (int d = 0; d + 1 < ndims; ++d) p.nrows *= m[d];
+  bool fused = p.fits && mode != kLatticeNever;
+  for (int d = 0; d < ndims; ++d) fused = fused && m[d] < ((size_t)1 << 31);
+  if (fused && mode == kLatticeAuto) {
+    const size_t wide = m_last > 64 ? m_last : 64;
+    fused = p.nrows >= (size_t)kLatticeWaves * (size_t)num_cus && n_last <= 4 * wide;
+  }
+  p.fused = fused;
+  p.lds_bytes = fused ? lds : 0;
+  return p;
+}
+
 // The LDS budget of the row kernel's lines: what the handle already grants rectilinear axis images
 // (Thresholds::axis_lds, or option "axis_lds_kb").
 inline size_t lattice_lds_budget(const LaunchConfig& c) {
@@ -171,5 +205,11 @@ hipError_t launch_lattice_expand(const GridDesc& g, const LatticeShape& s, const
 // groups of `group` fields, `lds_bytes` as fields_lattice_plan gives them; `layout`, `out_stride` as above.
 hipError_t launch_lattice_fields_rows(const GridDesc& g, const LatticeShape& s, const void* recs, size_t field_stride, size_t nfields,
                                       size_t group, void* out, size_t out_stride, int layout, size_t lds_bytes, hipStream_t stream);
+
+// k_lattice_grad.hip
+// The rows' values and gradient components (grad[d]: device, npoints elements each) from the records of
+// launch_lattice_axes; `lds_bytes` as lattice_grad_plan gives them.
+hipError_t launch_lattice_grad_rows(const GridDesc& g, const LatticeShape& s, const void* recs, void* out, void* const* grad,
+                                    size_t lds_bytes, hipStream_t stream);
 
 }  // namespace interpn

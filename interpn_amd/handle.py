@@ -461,12 +461,8 @@ class Interpolator:
         lens, n = _dims(axis_lens)
         _lib.raise_for_status(_lib.load().interpn_hip_reserve_lattice(self._h, lens, n, int(nstreams)))
 
-    def eval_lattice_host(self, axes, out: np.ndarray = None) -> np.ndarray:
-        """Evaluate on the lattice axes[0] x .. x axes[N-1] of host coordinate vectors (synchronous): the result has
-        shape `tuple(len(a) for a in axes)` and equals `eval_host` on `np.meshgrid(*axes, indexing="ij")`, bit for bit
-        (`interpn_hip_eval_lattice_host`).  On "Unrepresentable coordinate value" the AssertionError carries
-        `first_bad_index` (C order) and exactly the results in front of it have been written."""
-        lib = _lib.load()
+    def _lattice_host(self, axes, out):
+        """`(void** axes, lengths, count, shape, out)` of the host lattice forms: `axes` checked, `out` checked or made."""
         aptr, alen, naxes, _keep = _slice_of_slices("axes", axes, self.dtype)
         shape = tuple(int(alen[i]) for i in range(naxes))
         if out is None:
@@ -478,17 +474,10 @@ class Interpolator:
             raise ValueError("argument 'out': The given array is not contiguous")
         if not out.flags.writeable:
             raise ValueError("argument 'out': array is read-only")
-        vp = _args.void_pp(aptr)
-        bad = c_uint64(0)
-        st = lib.interpn_hip_eval_lattice_host(self._h, vp, alen, naxes, out.ctypes.data_as(c_void_p), ctypes.byref(bad))
-        _args.raise_for_indexed_status(st, bad)
-        return out
+        return _args.void_pp(aptr), alen, naxes, shape, out, _keep
 
-    def eval_lattice_tensors(self, axes, out=None, stream=None, no_alloc: bool = False):
-        """The same on torch CUDA tensors: `axes` are contiguous 1-D tensors of the handle's dtype, the result a tensor of
-        shape `tuple(len(a) for a in axes)`.  Asynchronous like `eval_tensors`; `finish()` synchronises and raises
-        for a coordinate the reference cannot evaluate, with `first_bad_index` in C order.  `.last_lattice_path` says
-        which path ran (`interpn_hip_eval_lattice_device`)."""
+    def _lattice_tensors(self, axes, out):
+        """`(axes, lengths, shape, out, device, dtype)` of the device lattice forms: `axes` checked, `out` checked or made."""
         want = _args.torch_dtype(self.dtype)
         axes = list(axes)
         dev = self.device()
@@ -505,16 +494,89 @@ class Interpolator:
             raise ValueError(f"out: expected shape {shape}, got {tuple(out.shape)}")
         else:
             _args.same_device("out", out, dev, "interpolator", True)
+        lens = (c_size_t * max(len(axes), 1))(*shape)
+        return axes, lens, shape, out, dev, want
+
+    def eval_lattice_host(self, axes, out: np.ndarray = None) -> np.ndarray:
+        """Evaluate on the lattice axes[0] x .. x axes[N-1] of host coordinate vectors (synchronous): the result has
+        shape `tuple(len(a) for a in axes)` and equals `eval_host` on `np.meshgrid(*axes, indexing="ij")`, bit for bit
+        (`interpn_hip_eval_lattice_host`).  On "Unrepresentable coordinate value" the AssertionError carries
+        `first_bad_index` (C order) and exactly the results in front of it have been written."""
+        lib = _lib.load()
+        vp, alen, naxes, _shape, out, _keep = self._lattice_host(axes, out)
+        bad = c_uint64(0)
+        st = lib.interpn_hip_eval_lattice_host(self._h, vp, alen, naxes, out.ctypes.data_as(c_void_p), ctypes.byref(bad))
+        _args.raise_for_indexed_status(st, bad)
+        return out
+
+    def eval_lattice_tensors(self, axes, out=None, stream=None, no_alloc: bool = False):
+        """The same on torch CUDA tensors: `axes` are contiguous 1-D tensors of the handle's dtype, the result a tensor of
+        shape `tuple(len(a) for a in axes)`.  Asynchronous like `eval_tensors`; `finish()` synchronises and raises
+        for a coordinate the reference cannot evaluate, with `first_bad_index` in C order.  `.last_lattice_path` says
+        which path ran (`interpn_hip_eval_lattice_device`)."""
+        axes, lens, _shape, out, dev, _want = self._lattice_tensors(axes, out)
         raw, owner = _args.resolve_stream(stream, dev)
-        n = len(axes)
-        lens = (c_size_t * max(n, 1))(*shape)
         path = ctypes.c_int(0)
-        st = _lib.load().interpn_hip_eval_lattice_device(self._h, _args.ptr_array(t.data_ptr() for t in axes), lens, n,
+        st = _lib.load().interpn_hip_eval_lattice_device(self._h, _args.ptr_array(t.data_ptr() for t in axes), lens, len(axes),
                                                          c_void_p(out.data_ptr()), c_void_p(int(raw)), _args.eval_flags(no_alloc),
                                                          ctypes.byref(path))
         _lib.raise_for_status(st)
         self._pending_streams[raw] = owner
         return out
+
+    # -- value and gradient on a lattice ---------------------------------------------------------
+    def eval_lattice_grad_host(self, axes, out: np.ndarray = None, grad: np.ndarray = None):
+        """Value and gradient on the lattice axes[0] x .. x axes[N-1] of host coordinate vectors (synchronous;
+        `interpn_hip_eval_lattice_grad_host`): returns `(out, grad)` of shapes `(*m)` and `(N, *m)`, m = the vectors'
+        lengths.  `out` has the bits of `eval_lattice_host`, `grad[d]` those of component d of `eval_grad_host`
+        (multilinear handles) or `eval_cubic_grad_host` (multicubic handles) on `np.meshgrid(*axes, indexing="ij")`; every
+        other handle raises "unsupported".  On "Unrepresentable coordinate value" the AssertionError carries
+        `first_bad_index` (C order) and exactly the entries of `out` and of every `grad[d]` in front of it have been
+        written."""
+        lib = _lib.load()
+        vp, alen, naxes, shape, out, _keep = self._lattice_host(axes, out)
+        if grad is None:
+            grad = np.zeros((naxes,) + shape, dtype=self.dtype)
+        self._host_grad(grad, (naxes,) + shape)
+        if not all(grad[d].flags.c_contiguous for d in range(naxes)):
+            raise ValueError("argument 'grad': every component grad[d] must be contiguous")
+        if not grad.flags.writeable:
+            raise ValueError("argument 'grad': array is read-only")
+        gp = _args.ptr_array(grad[d].ctypes.data for d in range(naxes))
+        bad = c_uint64(0)
+        st = lib.interpn_hip_eval_lattice_grad_host(self._h, vp, alen, naxes, out.ctypes.data_as(c_void_p), gp, ctypes.byref(bad))
+        _args.raise_for_indexed_status(st, bad)
+        return out, grad
+
+    def eval_lattice_grad_tensors(self, axes, out=None, grad=None, stream=None, no_alloc: bool = False):
+        """The same on torch CUDA tensors (`interpn_hip_eval_lattice_grad_device`): `axes` as for `eval_lattice_tensors`,
+        `grad` a tensor of shape `(N, *m)` whose components `grad[d]` are contiguous.  Asynchronous like `eval_tensors`; the scratch is that of
+        `eval_lattice_tensors`, so `reserve_lattice` serves `no_alloc=True` and graph capture here too.
+        `.last_lattice_path` says which path ran; `finish()` synchronises and raises for a coordinate the reference cannot
+        evaluate, with `first_bad_index` in C order."""
+        axes, lens, shape, out, dev, want = self._lattice_tensors(axes, out)
+        k = len(axes)
+        if grad is None:
+            import torch
+
+            grad = torch.empty((k,) + shape, dtype=want, device=torch.device("cuda", dev))
+        elif not (hasattr(grad, "is_cuda") and grad.is_cuda and grad.dtype == want):
+            raise TypeError(f"grad: expected a {want} CUDA tensor")
+        elif tuple(grad.shape) != (k,) + shape:
+            raise ValueError(f"grad: expected shape {(k,) + shape}, got {tuple(grad.shape)}")
+        elif not all(grad[d].is_contiguous() for d in range(k)):
+            raise TypeError("grad: every component grad[d] must be contiguous")
+        else:
+            _args.same_device("grad", grad, dev, "interpolator", True)
+        raw, owner = _args.resolve_stream(stream, dev)
+        path = ctypes.c_int(0)
+        gp = _args.ptr_array(grad[d].data_ptr() for d in range(k))
+        st = _lib.load().interpn_hip_eval_lattice_grad_device(self._h, _args.ptr_array(t.data_ptr() for t in axes), lens, k,
+                                                              c_void_p(out.data_ptr()), gp, c_void_p(int(raw)),
+                                                              _args.eval_flags(no_alloc), ctypes.byref(path))
+        _lib.raise_for_status(st)
+        self._pending_streams[raw] = owner
+        return out, grad
 
     def check_bounds_tensors(self, obs, atol: float, stream=None) -> np.ndarray:
         """`check_bounds` on torch CUDA tensors against this interpolator's grid: one flag per
