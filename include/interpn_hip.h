@@ -680,6 +680,56 @@ int interpn_hip_fields_eval_points_host(interpn_hip_fields* fields, const void* 
  * well, which a set does not expose: under NO_ALLOC they evaluate in place). */
 int interpn_hip_fields_reserve_points(interpn_hip_fields* fields, size_t npoints, int nstreams);
 
+/* Point-major gradients of a field set — the points as ONE (npoints, N) array, the K values as ONE (npoints, K) array and
+ * their Jacobian as ONE (npoints, K, N) array: particle positions or a model's (..., N) tensor in, a feature vector and its
+ * derivative with respect to the position out, without a transpose on either side.
+ *
+ * Definition  coordinate d of point i is pts[i * point_stride + d], as for interpn_hip_fields_eval_points_* (elements
+ *           d >= ndims of a row are never read).  out[i * out_stride + f] has the bits of interpn_hip_fields_eval_points_*
+ *           (those of interpn_hip_fields_eval_* on the columns); jac[i * jac_stride + f * ndims + d] has the bits of
+ *           grad[(f * ndims + d) * grad_stride + i] of interpn_hip_fields_eval_grad_* on the columns, in both fma flavours.
+ *           Strides in ELEMENTS, out_stride >= nfields, jac_stride >= nfields * ndims; elements of a row beyond its first
+ *           K (values) or K * ndims (Jacobian) are never written.  The three blocks must not overlap.
+ * Paths     FUSED (sets with the fused table: multilinear N = 2, 3): one launch of interpn::k_linear_fields_points_grad on
+ *           that table — the row load of k_linear_fields_points, the cell search, piece fetch and N + 1 trees per field of
+ *           k_linear_fields_grad, and per line group a point-major LDS tile from which a point's min(P, K - f0) values and
+ *           min(P, K - f0) * N components are stored lane-contiguously (jac_stride == K * N and one line group: one run of
+ *           64 K N elements per wave).  The cell widths travel through LDS beside t[N] and the storing lane does the one
+ *           division of a component.  No scratch, never allocates, can be captured into a graph.
+ *           SPLIT (every multicubic set, multilinear N = 1 and 4..8, sets without the table, "fused" = 0, "points_path" =
+ *           2): per slice interpn::k_split_points de-interleaves the rows into scratch, interpn_hip_fields_eval_grad_device
+ *           evaluates them into K + K N scratch rows (fused or per field by its own rule), interpn::k_join_fields writes
+ *           the value rows and, with K N "fields", the Jacobian rows.  One scratch block, from the first field's handle,
+ *           holds a slice: N + K (N + 1) arrays within 64 MiB together, 256 points at least.  Under graph capture or with
+ *           INTERPN_HIP_EVAL_NO_ALLOC only reserved blocks are used (INTERPN_HIP_ERR_OUT_OF_MEMORY without one);
+ *           interpn_hip_fields_reserve_points_grad provides them.
+ *           Reported with INTERPN_HIP_FIELDS_POINTS_PATH_* through *path_taken and the option "last_points_path";
+ *           interpn_hip_fields_kernel_name says "interpn::k_linear_fields_points_grad<double, 3, false, true>" after a
+ *           fused call.
+ * Options   "points_path" (-1, 1, 2) and "points_slice" mean what they mean for interpn_hip_fields_eval_points_*; "fused"
+ *           what it means for interpn_hip_fields_eval_grad_*.  Automatic: fused wherever the set has the table and "fused"
+ *           is not 0, except sets of two fields per table line and four line groups or more (3-D f64, K >= 7), where the
+ *           fused kernel measured level with the split path at best.
+ * Checks    before any device work, in this order: fields NULL: INTERPN_HIP_ERR_INVALID_ARGUMENT; a nearest set:
+ *           INTERPN_HIP_ERR_UNSUPPORTED; point_stride < ndims, out_stride < nfields, jac_stride < nfields * ndims:
+ *           INTERPN_HIP_ERR_INVALID_ARGUMENT; npoints == 0: INTERPN_HIP_OK whatever the pointers are; pts, out or jac NULL,
+ *           or a block whose bytes do not fit size_t: INTERPN_HIP_ERR_INVALID_ARGUMENT; unknown flags:
+ *           INTERPN_HIP_ERR_INVALID_ARGUMENT; "points_path" = 1 without the table: INTERPN_HIP_ERR_UNSUPPORTED.
+ * Failing   device form: interpn_hip_fields_finish reports the first failing point of the whole call, on every path.  Host
+ * points    form: the set's status; exactly rows [0, i) of both blocks are written, their first K and K * ndims elements
+ *           only, everything else is left as it was. */
+/* Asynchronous on `stream`; `pts`, `out`, `jac`: device.  `flags`: INTERPN_HIP_EVAL_NO_ALLOC.  *path_taken (may be NULL). */
+int interpn_hip_fields_eval_points_grad_device(interpn_hip_fields* fields, const void* pts, size_t point_stride, size_t npoints,
+                                               void* out, size_t out_stride, void* jac, size_t jac_stride, void* stream,
+                                               unsigned flags, int* path_taken);
+/* The same on host arrays, synchronous: chunks of 2 Mi points (option "host_chunk"), a chunk's rows uploaded with one copy,
+ * only the first K and K * ndims elements of the rows in front of a failing point downloaded. */
+int interpn_hip_fields_eval_points_grad_host(interpn_hip_fields* fields, const void* pts, size_t point_stride, size_t npoints,
+                                             void* out, size_t out_stride, void* jac, size_t jac_stride);
+/* Scratch blocks for split-path evaluations of up to `npoints` points on up to `nstreams` concurrent streams (blocks of
+ * the first field's handle). */
+int interpn_hip_fields_reserve_points_grad(interpn_hip_fields* fields, size_t npoints, int nstreams);
+
 /* ------------------------------------------------------------------------------------------
  * Lattice evaluation — the points are the tensor product of N coordinate vectors, one per axis: re-gridding,
  * RegularGridInterpolator on a meshgrid, resampling a volume, refining a table.  The caller passes the N vectors

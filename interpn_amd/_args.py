@@ -126,6 +126,53 @@ def row_stride(name: str, n: int, width: int, strides, exc, unit_msg: str, strid
     return width
 
 
+def point_rows(name: str, pts, nd: int):
+    """The rows of point-major `pts`, a numpy array or a torch tensor of shape `(..., nd)` whose type and dtype the caller
+    has checked: `(rows, n, stride, lead)`.  A 2-D array with unit stride along a row and rows a whole number of elements
+    >= `nd` apart (`buf[:, :3]` of an `(n, 4)` block) is taken as it is; anything else is copied once."""
+    shape = tuple(int(v) for v in pts.shape)
+    if len(shape) < 1 or shape[-1] != nd:
+        raise ValueError(f"{name}: expected shape (..., {nd}), got {shape}")
+    host = isinstance(pts, np.ndarray)
+    strides = elem_strides(pts) if host else [int(v) for v in pts.stride()]
+    if len(shape) == 2 and (nd == 1 or strides[1] == 1) and (shape[0] <= 1 or strides[0] >= nd):
+        rows = pts
+    else:
+        rows = np.ascontiguousarray(pts).reshape(-1, nd) if host else pts.contiguous().reshape(-1, nd)
+        strides = [nd, 1]
+    n = int(rows.shape[0])
+    return rows, n, (strides[0] if n > 1 else nd), shape[:-1]
+
+
+def point_results(name: str, a, lead, tail, n: int) -> int:
+    """The row stride, in elements, of the point-major result block `a` (the argument `name`; a numpy array or a torch tensor
+    whose type and dtype the caller has checked) of shape `lead + tail`: a contiguous block, or with one leading axis a view
+    whose rows are contiguous runs of prod(tail) elements a whole number of elements >= that apart — a row's other elements
+    stay untouched."""
+    shape = tuple(int(v) for v in a.shape)
+    want = tuple(lead) + tuple(tail)
+    if shape != want:
+        raise ValueError(f"{name}: expected shape {want}, got {shape}")
+    width = int(np.prod(tail, dtype=np.int64))
+    host = isinstance(a, np.ndarray)
+    strides = elem_strides(a) if host else [int(v) for v in a.stride()]
+    if len(lead) != 1:
+        if not (a.flags.c_contiguous if host else a.is_contiguous()):
+            raise ValueError(f"{name}: expected a contiguous block, or one leading axis and contiguous rows")
+        return width
+    if n:
+        run = 1
+        for extent, st in zip(reversed(tail), reversed(strides[1:])):  # the row itself: C order, unit inner stride
+            if extent > 1 and st != run:
+                raise ValueError(f"{name}: every row must be contiguous (unit stride along the last axis)")
+            run *= extent
+    if n > 1:
+        if strides[0] < width:
+            raise ValueError(f"{name}: the row stride must be a whole number of elements, at least {width}")
+        return strides[0]
+    return width
+
+
 def first_bad_error(status: int, index: int) -> AssertionError:
     """The error of a status that carries a first failing index (`_lib.UNREPRESENTABLE`)."""
     err = AssertionError(_lib.strerror(status))

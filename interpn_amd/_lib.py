@@ -194,6 +194,11 @@ def load() -> ctypes.CDLL:
                                                           ctypes.c_uint, POINTER(c_int)]
     lib.interpn_hip_fields_eval_points_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t]
     lib.interpn_hip_fields_reserve_points.argtypes = [c_void_p, c_size_t, c_int]
+    lib.interpn_hip_fields_eval_points_grad_device.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p,
+                                                               c_size_t, c_void_p, ctypes.c_uint, POINTER(c_int)]
+    lib.interpn_hip_fields_eval_points_grad_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p,
+                                                             c_size_t]
+    lib.interpn_hip_fields_reserve_points_grad.argtypes = [c_void_p, c_size_t, c_int]
     lib.interpn_hip_fields_eval_lattice_device.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_size_t,
                                                            c_int, c_void_p, ctypes.c_uint, POINTER(c_int)]
     lib.interpn_hip_fields_eval_lattice_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_size_t,

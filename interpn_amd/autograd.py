@@ -12,6 +12,9 @@ graph: the gradient with respect to `vals` is not built.
 `interp_fields(fs, obs)` is `interp` for a field set (`Fields`): a `(K, *shape)` tensor whose forward pass is one
 `Fields.eval_grad_tensors`; the saved Jacobian turns the incoming `(K, *shape)` gradient into one gradient per coordinate.
 
+`interp_fields_points(fs, pts)` is `interp_fields` for positions kept as ONE tensor of shape `(..., N)`: a `(..., K)` tensor
+whose forward pass is one `Fields.eval_points_grad_tensors`; `pts.grad` has the shape of `pts`.
+
 `interp_lattice(it, axes)` is `interp` on the lattice axes[0] x .. x axes[N-1]: its forward pass is one
 `Interpolator.eval_lattice_grad_tensors`; the backward pass sums the incoming `(*m)` gradient times component d over every
 lattice dimension but d, which gives one gradient per coordinate VECTOR.
@@ -24,6 +27,7 @@ from __future__ import annotations
 _FUNCTION = None
 _POINTS_FUNCTION = None
 _FIELDS_FUNCTION = None
+_FIELDS_POINTS_FUNCTION = None
 _LATTICE_FUNCTION = None
 
 
@@ -137,6 +141,42 @@ def interp_fields(fs, obs):
     tensors of the set's dtype): a tensor of shape `(K, *obs[0].shape)`, differentiable with respect to every tensor of `obs`.
     The table stays a constant of the graph."""
     return _fields_function().apply(fs, *obs)
+
+
+def _fields_points_function():
+    """The point-major field-set torch.autograd.Function, built on first use like `_function`."""
+    global _FIELDS_POINTS_FUNCTION
+    if _FIELDS_POINTS_FUNCTION is not None:
+        return _FIELDS_POINTS_FUNCTION
+    import torch
+
+    class _InterpFieldsPoints(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fs, pts):
+            shape = pts.shape
+            flat = pts.detach().reshape(-1, shape[-1])
+            out, jac = fs.eval_points_grad_tensors(flat)
+            fs.finish()
+            ctx.save_for_backward(jac)
+            ctx.pts_shape = shape
+            return out.reshape(tuple(shape[:-1]) + (out.shape[-1],))
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            (jac,) = ctx.saved_tensors  # (n, K, N)
+            g = grad_out.reshape(jac.shape[0], jac.shape[1])
+            # einsum("...k,...kn->...n"): pts.grad[i, d] = sum_f grad_out[i, f] * J[i, f, d], products first, then their sum
+            return None, (g.unsqueeze(-1) * jac).sum(-2).reshape(ctx.pts_shape)
+
+    _FIELDS_POINTS_FUNCTION = _InterpFieldsPoints
+    return _FIELDS_POINTS_FUNCTION
+
+
+def interp_fields_points(fs, pts):
+    """Values of the field set `fs` (a multilinear or multicubic `Fields`) at the points `pts`, ONE torch CUDA tensor of shape
+    `(..., N)` of the set's dtype: a tensor of shape `(..., K)`, differentiable with respect to `pts`.  The table stays a
+    constant of the graph."""
+    return _fields_points_function().apply(fs, pts)
 
 
 def _lattice_function():

@@ -17,9 +17,15 @@ namespace {
 // gradients".
 bool grad_auto_takes_fused(const interpn_hip_fields* s) { return s->table != nullptr; }
 
+}  // namespace
+
+namespace interpn_abi {
 bool grad_takes_fused(const interpn_hip_fields* s) {
   return s->table && (s->fused == 1 || (s->fused < 0 && grad_auto_takes_fused(s)));
 }
+}  // namespace interpn_abi
+
+namespace {
 
 // What both entry points check before any device work, in the order of interpn_hip_fields_eval_device / _host.
 int fields_grad_checks(const interpn_hip_fields* s, const void* const* obs, const size_t* obs_lens, bool need_lens, size_t nobs,

@@ -13,6 +13,8 @@
 //   abi_grad.hip      value and gradient of a multilinear or multicubic handle (eval_grad_* / eval_cubic_grad_*)
 //   abi_fields.hip    field sets: creation, column and point-major forms, options
 //   abi_fields_grad.hip  values and Jacobian of a field set (fields_eval_grad_device / _host)
+//   abi_fields_points_grad.hip  point-major values and Jacobian of a field set (fields_eval_points_grad_device / _host,
+//                     fields_reserve_points_grad)
 //   abi_fields_lattice.hip  field sets on a lattice (fields_eval_lattice_device / _host, fields_reserve_lattice, fields_lattice_plan)
 //   abi_lattice_grad.hip  value and gradient on a lattice (eval_lattice_grad_device / _host, lattice_grad_plan)
 //   scratch_slots.h   (no HIP in it) scratch blocks between streams and stream marks: settle / take / release / reserve /
@@ -436,6 +438,10 @@ constexpr size_t kExpandSliceMin = (size_t)1 << 16;     // ... but never fewer p
 
 // abi_fields.hip
 int ensure_sub_tables(interpn_hip_fields* s);
+
+// abi_fields_grad.hip: whether the column form's value-and-Jacobian evaluation runs its fused kernel (option "fused" and
+// its rule) — the point-major split path (abi_fields_points_grad.hip) parks one status word or all K by it
+bool grad_takes_fused(const interpn_hip_fields* s);
 
 // abi_grad.hip: the column form's gradient launch, k_linear_grad / k_cubic_grad or the runtime-N kernels by the handle's
 // method and each launcher's own rule (also the middle step of the point-major split path, abi_points.hip)

@@ -327,6 +327,11 @@ hipError_t launch_linear_fields_points(const GridDesc& g, const void* table, int
                                        size_t out_stride, size_t npts, unsigned long long* first_bad, hipStream_t stream);
 hipError_t launch_join_fields(const GridDesc& g, const void* src, size_t pitch, size_t nfields, void* out, size_t out_stride,
                               size_t count, hipStream_t stream);
+// Point-major values and Jacobian of a set in one pass (k_fields_points_grad.hip, linear_fields_points_grad.h) on the same
+// table: field f of point i to out[i * out_stride + f], its component d to jac[i * jac_stride + f * ndims + d] (elements).
+hipError_t launch_linear_fields_points_grad(const GridDesc& g, const void* table, int nfields, const void* pts, size_t stride,
+                                            void* out, size_t out_stride, void* jac, size_t jac_stride, size_t npts,
+                                            unsigned long long* first_bad, hipStream_t stream);
 
 // 1-D multilinear-rectilinear from per-bucket records (k_linear1_records.hip).
 size_t records1_bytes(const GridDesc& g, int M);

@@ -437,6 +437,86 @@ class Fields:
             raise TypeError(f"eval_points on a host array takes no {sorted(kwargs)}")
         return self.eval_points_host(pts, out)
 
+    # -- point-major values and Jacobian: (n, N) points in, (n, K) values and (n, K, N) Jacobian out ----
+    def reserve_points_grad(self, npoints: int, nstreams: int = 1) -> None:
+        """`reserve_points` for `eval_points_grad_*` (`interpn_hip_fields_reserve_points_grad`): a slice of the split path
+        holds N + K (N + 1) arrays.  The fused kernel (sets with the fused table) needs none."""
+        _lib.raise_for_status(_lib.load().interpn_hip_fields_reserve_points_grad(self._h, int(npoints), int(nstreams)))
+
+    def eval_points_grad_host(self, pts, out=None, jac=None):
+        """Every field and its gradient at the rows of a host array of shape `(n, N)` or `(..., N)` (synchronous;
+        `interpn_hip_fields_eval_points_grad_host`): `(out, jac)` of shapes `(..., K)` and `(..., K, N)`; `out[i, f]` has the
+        bits of `eval_points_host`, `jac[i, f, d]` those of `eval_grad_host(columns)[1][f, d, i]`.  `pts` is taken as
+        `eval_points_host` takes it.  `out` and `jac` may be 2-D / 3-D views with any row stride >= K / K N and contiguous
+        rows; a row's other elements are not touched.  On "Unrepresentable coordinate value" exactly the rows in front of
+        the failing point are written, in both blocks."""
+        _args.check_ndarray("pts", pts, self.dtype)
+        nd, k = self._ndims, self.nfields
+        rows, n, stride, lead = _args.point_rows("argument 'pts'", pts, nd)
+        if out is None:
+            out = np.zeros(lead + (k,), dtype=self.dtype)
+        if jac is None:
+            jac = np.zeros(lead + (k, nd), dtype=self.dtype)
+        for name, a in (("out", out), ("jac", jac)):
+            if not isinstance(a, np.ndarray) or a.dtype != self.dtype:
+                raise TypeError(f"{name}: expected a numpy array of {self.dtype.name}")
+        ostride = _args.point_results("out", out, lead, (k,), n)
+        jstride = _args.point_results("jac", jac, lead, (k, nd), n)
+        if not (out.flags.writeable and jac.flags.writeable):
+            raise ValueError("out, jac: array is read-only")
+        st = _lib.load().interpn_hip_fields_eval_points_grad_host(self._h, c_void_p(rows.ctypes.data), stride, n,
+                                                                 c_void_p(out.ctypes.data), ostride, c_void_p(jac.ctypes.data), jstride)
+        self._took_points()
+        _lib.raise_for_status(st)
+        return out, jac
+
+    def eval_points_grad_tensors(self, pts, out=None, jac=None, stream=None, no_alloc: bool = False):
+        """The same on a torch CUDA tensor (asynchronous on torch's current stream unless given;
+        `interpn_hip_fields_eval_points_grad_device`): no `pts.T.contiguous()` in front and no permuted copy of the values
+        or the Jacobian behind; everything stays on the device.  `pts`, `out` and `jac` must not overlap.  Sets with the
+        fused table run one launch of `interpn::k_linear_fields_points_grad`, which allocates nothing and can be captured
+        into a graph; `last_points_path` says which path ran; `finish()` synchronises and surfaces "Unrepresentable
+        coordinate value"."""
+        want = _args.torch_dtype(self.dtype)
+        nd, k = self._ndims, self.nfields
+        if not (hasattr(pts, "is_cuda") and pts.is_cuda and pts.dtype == want):
+            raise TypeError(f"pts: expected a {want} CUDA tensor of shape (..., {nd})")
+        dev = self.device()
+        rows, n, stride, lead = _args.point_rows("pts", pts, nd)
+        _args.same_device("pts", pts, dev, "set")
+        if out is None or jac is None:
+            import torch
+
+            if out is None:
+                out = torch.empty(lead + (k,), dtype=want, device=torch.device("cuda", dev))
+            if jac is None:
+                jac = torch.empty(lead + (k, nd), dtype=want, device=torch.device("cuda", dev))
+        for name, a in (("out", out), ("jac", jac)):
+            if not (hasattr(a, "is_cuda") and a.is_cuda and a.dtype == want):
+                raise TypeError(f"{name}: expected a {want} CUDA tensor")
+            _args.same_device(name, a, dev, "set")
+        ostride = _args.point_results("out", out, lead, (k,), n)
+        jstride = _args.point_results("jac", jac, lead, (k, nd), n)
+        raw, owner = _args.resolve_stream(stream, dev)
+        path = ctypes.c_int(0)
+        st = _lib.load().interpn_hip_fields_eval_points_grad_device(self._h, c_void_p(rows.data_ptr()), stride, n,
+                                                                   c_void_p(out.data_ptr()), ostride, c_void_p(jac.data_ptr()),
+                                                                   jstride, c_void_p(int(raw)), _args.eval_flags(no_alloc),
+                                                                   ctypes.byref(path))
+        _lib.raise_for_status(st)
+        if n:
+            self._took_points()
+        self._pending_streams[raw] = owner
+        return out, jac
+
+    def eval_points_grad(self, pts, out=None, jac=None, **kwargs):
+        """`eval_points_grad_tensors` for a torch tensor, `eval_points_grad_host` for a numpy array."""
+        if _is_tensor(pts):
+            return self.eval_points_grad_tensors(pts, out, jac, **kwargs)
+        if kwargs:
+            raise TypeError(f"eval_points_grad on a host array takes no {sorted(kwargs)}")
+        return self.eval_points_grad_host(pts, out, jac)
+
     # -- lattice evaluation: one coordinate vector per axis in, (K, *m) or (*m, K) values out ----
     @property
     def last_lattice_path(self):
@@ -689,12 +769,9 @@ def interpn_fields_grad(obs, grids, vals, *, method="linear", field_axis: int = 
     return (np.ascontiguousarray(np.moveaxis(out, 0, -1)), np.ascontiguousarray(np.moveaxis(np.moveaxis(jac, 0, -1), 0, -1)))
 
 
-def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, linearize_extrapolation: bool = True,
-                          assume_regular: bool = False, check_bounds: bool = False, bounds_atol: float = 1e-8):
-    """scipy's `interpn(points, values, xi)` with trailing value dimensions: `vals` of shape (*dims, K), `xi` of shape
-    (..., N) — a numpy array or a torch CUDA tensor — and a result of shape (..., K).  The rules are those of
-    `interpn_fields` (dtype from `vals`, exact-spacing regularity test); the points and the result keep their layout
-    (`Fields.eval_points`), and the value table is re-laid field-major once, as part of setting the fields up."""
+def _xi_of_fields(xi, grids, vals, method, out):
+    """What `interpn_fields_points` and `interpn_fields_points_grad` check and work out before they differ:
+    `(dtype, grids, nd, k, nper, on_device)`."""
     _setup.check_method(method)
     dtype = _setup.field_values_dtype(vals, "a trailing field axis")
     if not (isinstance(xi, np.ndarray) or _is_tensor(xi)):
@@ -718,6 +795,16 @@ def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, lineari
         raise ValueError(f"out: expected shape {rshape}, got {tuple(out.shape)}")
     if _is_tensor(xi) and not on_device:
         raise TypeError("xi: expected a numpy array or a torch CUDA tensor")
+    return dtype, grids, nd, k, nper, on_device
+
+
+def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, linearize_extrapolation: bool = True,
+                          assume_regular: bool = False, check_bounds: bool = False, bounds_atol: float = 1e-8):
+    """scipy's `interpn(points, values, xi)` with trailing value dimensions: `vals` of shape (*dims, K), `xi` of shape
+    (..., N) — a numpy array or a torch CUDA tensor — and a result of shape (..., K).  The rules are those of
+    `interpn_fields` (dtype from `vals`, exact-spacing regularity test); the points and the result keep their layout
+    (`Fields.eval_points`), and the value table is re-laid field-major once, as part of setting the fields up."""
+    dtype, grids, nd, k, nper, on_device = _xi_of_fields(xi, grids, vals, method, out)
     device = _setup.device_index(xi) if on_device else -1
     vals = _setup.field_major(vals, k, nper, True, on_device)
     spec = _setup.regular_spec(grids, dtype, assume_regular)
@@ -737,3 +824,25 @@ def interpn_fields_points(xi, grids, vals, *, method="linear", out=None, lineari
         fs.close()
     return res
 
+
+def interpn_fields_points_grad(xi, grids, vals, *, method="linear", linearize_extrapolation: bool = True,
+                               assume_regular: bool = False):
+    """`interpn_fields_points()` with the Jacobian: `vals` of shape (*dims, K), `xi` of shape (..., N) — a numpy array or a
+    torch CUDA tensor — and `(out, jac)` of shapes (..., K) and (..., K, N), `jac[..., f, d]` the derivative of field f with
+    respect to coordinate d, with the bits of `interpn_fields_grad` on the columns.  The points and both results keep their
+    layout (`Fields.eval_points_grad`): one pass where the set has the fused kernel.  `method` is "linear" or "cubic"
+    ("nearest" has no gradient: the library's "unsupported" error)."""
+    dtype, grids, nd, k, nper, on_device = _xi_of_fields(xi, grids, vals, method, None)
+    device = _setup.device_index(xi) if on_device else -1
+    vals = _setup.field_major(vals, k, nper, True, on_device)
+    fs = _setup.create(Fields, method, grids, _setup.regular_spec(grids, dtype, assume_regular), vals, dtype, device,
+                       linearize_extrapolation=linearize_extrapolation)
+    try:
+        if on_device:
+            res = fs.eval_points_grad_tensors(xi)
+            fs.finish()
+        else:
+            res = fs.eval_points_grad_host(xi)
+    finally:
+        fs.close()
+    return res
