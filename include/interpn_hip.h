@@ -907,6 +907,78 @@ int interpn_hip_fields_lattice_plan(size_t elem_size, int method, size_t ndims, 
                                     size_t nfields, int layout, int* path, size_t* group, size_t* lds_bytes, size_t* npoints);
 
 /* ------------------------------------------------------------------------------------------
+ * Field-set gradients on a lattice — the values of K fields AND their K x N Jacobian on the tensor product of N coordinate
+ * vectors in one pass: the Jacobian (and its determinant) of a displacement field resampled onto a finer mesh, the
+ * velocity-gradient tensor of a re-gridded vector field, the per-channel gradients of a resized (H, W, C) image, the partial
+ * derivatives of all K quantities of a refined table.  `axes`, `axis_lens`, `naxes` as for interpn_hip_eval_lattice_device.
+ *
+ * Layouts   the two of "Field sets on a lattice", strides in ELEMENTS, p the lattice index in C order, d the coordinate:
+ *           INTERPN_HIP_FIELDS_LATTICE_FIELD_MAJOR: out[f * out_stride + p], shape (K, *m), and
+ *           jac[(f * N + d) * jac_stride + p], shape (K, N, *m); both strides >= prod(axis_lens) — the convention of
+ *           interpn_hip_fields_eval_grad_device.
+ *           INTERPN_HIP_FIELDS_LATTICE_FIELDS_LAST: out[p * out_stride + f], shape (*m, K), out_stride >= K, and
+ *           jac[p * jac_stride + f * N + d], shape (*m, K, N), jac_stride >= K * N — the convention of
+ *           interpn_hip_fields_eval_points_grad_device.
+ *           Nothing is written outside those elements: padding columns of a wider row stay as they were.  `out`, `jac`
+ *           and the axes must not overlap.
+ * Contract  nothing new is defined: out for (f, p) has the bits of interpn_hip_fields_eval_lattice_device (and so of
+ *           interpn_hip_eval_lattice_device on the handle of field f alone), and jac for (f, d, p) the bits of grad[d][p] of
+ *           interpn_hip_eval_lattice_grad_device on the handle of field f alone, on both paths, in both fma flavours, in
+ *           f64 and f32, on regular and rectilinear grids.
+ * Paths     FUSED (multilinear and multicubic, N = 2 or 3, grids that 32 bits index): ONE launch of interpn::k_lattice_axes
+ *           on the first field's description, then ONE launch of interpn::k_lattice_fields_grad_rows — the field loop,
+ *           groups and tile of interpn::k_lattice_fields_rows around the L lines per field of interpn::k_lattice_grad_rows
+ *           (multilinear L = N + 1, multicubic L = N).  A wave owns a row and G x L packed lines; per chunk of 64 outputs a
+ *           lane loads the last axis's record, width and sign once and computes, per field of the group, the value and the
+ *           N components (one IEEE division each).  Field-major results leave as N + 1 coalesced stores per field;
+ *           fields-last results through a [64] x P LDS tile, P = (G (N + 1)) | 1, as contiguous runs (where jac_stride ==
+ *           K N == G N: one run of 64 K N elements per wave and chunk).  G = the largest g <= min(K, 8) with
+ *           4 * (round16(g * L * n_{N-1} * sizeof(T)) + tile(g)) within the LDS budget "axis_lds_kb", tile(g) =
+ *           round16(64 * ((g (N + 1)) | 1) * sizeof(T)) for fields-last and 0 for field-major results; K > G: ceil(K / G)
+ *           passes per row.  At the default 20 KiB a fields-last f64 3-D call never has G > 2 (and G = 2 only for last grid
+ *           axes of at most 8 or 10 entries): the tile takes the room, and "axis_lds_kb" is the knob.  Takes a records
+ *           block of the FIRST field's handle under the rules of interpn_hip_eval_lattice_device; capturable after
+ *           interpn_hip_fields_reserve_lattice_grad; builds none of the handles' deferred tables.
+ *           PER_FIELD (everything else: N = 1, N >= 4, a line beyond the budget, "lattice" = 0, "force_generic", grids 32
+ *           bits do not index): K calls of interpn_hip_eval_lattice_grad_device's path through the K handles.  Field-major
+ *           results go straight into the caller's rows (grad[d] = jac + (f * N + d) * jac_stride); fields-last results
+ *           go, per slice of whole leading-axis indices (K (N + 1) rows within 64 MiB together, one index at least;
+ *           option "points_slice" = points, for tests), into scratch rows of the first handle and through two launches of
+ *           interpn::k_join_fields, K rows into `out` and K N rows into `jac`.
+ * Options   "lattice" and "axis_lds_kb" as for the value form; automatic mode applies the rules of
+ *           interpn_hip_eval_lattice_grad_device and G >= 1, no rule of its own.  "last_lattice_path"
+ *           and "last_lattice_group" are updated; interpn_hip_fields_kernel_name reports
+ *           "interpn::k_lattice_fields_grad_rows<T, method, N, rectilinear, fma, fields_last>" after a fused evaluation.
+ * Checks    before any device work, in this order: fields NULL: INTERPN_HIP_ERR_INVALID_ARGUMENT; the checks of
+ *           interpn_hip_fields_eval_lattice_device on the lattice in their order (an empty axis: INTERPN_HIP_OK, nothing
+ *           written); a nearest set: INTERPN_HIP_ERR_UNSUPPORTED; then `jac` NULL, a layout value other than the two, a
+ *           stride below its minimum, or a result whose bytes do not fit size_t: INTERPN_HIP_ERR_INVALID_ARGUMENT.
+ * Failing   as for "Field sets on a lattice": one first failing index in C order for every field, through
+ * points    interpn_hip_fields_finish on both paths (the fused path uses the first handle's word).
+ * ---------------------------------------------------------------------------------------- */
+/* Asynchronous on `stream`.  `axes`: HOST array of `naxes` DEVICE pointers; `out`, `jac`: device.  `flags`:
+ * INTERPN_HIP_EVAL_NO_ALLOC.  *path_taken (may be NULL): INTERPN_HIP_FIELDS_LATTICE_PATH_*. */
+int interpn_hip_fields_eval_lattice_grad_device(interpn_hip_fields* fields, const void* const* axes, const size_t* axis_lens,
+                                                size_t naxes, void* out, size_t out_stride, void* jac, size_t jac_stride,
+                                                int layout, void* stream, unsigned flags, int* path_taken);
+/* The same on host arrays, synchronous: chunks of leading-axis indices of about 2^25 / (K (N + 1)) points each (option
+ * "host_chunk": points per chunk).  On a failing point the status is the set's, *first_bad_index (may be NULL) = i in C
+ * order over the whole lattice, and exactly the results in front of it are written, in both layouts: out[f][0..i) and
+ * jac[f][d][0..i) (field-major), rows [0, i) of `out` and `jac` (fields-last); everything else is left as it was.  Shares
+ * the sticky status words with the device form: finish device evaluations first. */
+int interpn_hip_fields_eval_lattice_grad_host(interpn_hip_fields* fields, const void* const* axes, const size_t* axis_lens,
+                                              size_t naxes, void* out, size_t out_stride, void* jac, size_t jac_stride,
+                                              int layout, uint64_t* first_bad_index);
+/* interpn_hip_fields_reserve_lattice for value-and-Jacobian calls: the per-field path's slice holds K (N + 1) rows.  The
+ * same limit: a per-field evaluation with fields-last results holds two of the first handle's four blocks at a time, so for
+ * THAT form the guarantee covers two concurrent streams.  A nearest set: INTERPN_HIP_ERR_UNSUPPORTED.  Synchronous. */
+int interpn_hip_fields_reserve_lattice_grad(interpn_hip_fields* fields, const size_t* axis_lens, size_t naxes, int nstreams);
+/* interpn_hip_fields_lattice_plan for a value-and-Jacobian call (no device; the same arguments, environment latches and
+ * statuses), except that the nearest method has no gradient: INTERPN_HIP_ERR_UNSUPPORTED. */
+int interpn_hip_fields_lattice_grad_plan(size_t elem_size, int method, size_t ndims, const size_t* dims, const size_t* axis_lens,
+                                         size_t nfields, int layout, int* path, size_t* group, size_t* lds_bytes, size_t* npoints);
+
+/* ------------------------------------------------------------------------------------------
  * Point-major observation points — the points as ONE array of shape (npoints, N), the layout of particle positions, ray
  * samples and scipy's `xi`, instead of N coordinate arrays.
  *

@@ -18,8 +18,8 @@ from ._setup import check_regular as _check_regular
 from ._setup import is_cuda_tensor as _is_cuda_tensor
 from .classes import (MulticubicRectilinear, MulticubicRegular, MultilinearRectilinear, MultilinearRegular,
                       NearestRectilinear, NearestRegular)
-from .fields import (Fields, fields_lattice_plan, fields_layout, interpn_fields, interpn_fields_grad, interpn_fields_lattice,
-                     interpn_fields_points, interpn_fields_points_grad)
+from .fields import (Fields, fields_lattice_grad_plan, fields_lattice_plan, fields_layout, interpn_fields, interpn_fields_grad,
+                     interpn_fields_lattice, interpn_fields_lattice_grad, interpn_fields_points, interpn_fields_points_grad)
 from .handle import Interpolator, eval_device_sharded, eval_host_sharded
 
 __version__ = "0.1.0"
@@ -45,6 +45,7 @@ __all__ = [
     "interpn_fields",
     "interpn_fields_grad",
     "interpn_fields_lattice",
+    "interpn_fields_lattice_grad",
     "interpn_fields_points",
     "interpn_fields_points_grad",
     "interpn_grad",
@@ -56,6 +57,7 @@ __all__ = [
     "lattice_grad_plan",
     "Fields",
     "fields_lattice_plan",
+    "fields_lattice_grad_plan",
     "fields_layout",
     "Interpolator",
     "MultilinearRegular",

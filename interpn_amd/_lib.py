@@ -206,6 +206,13 @@ def load() -> ctypes.CDLL:
     lib.interpn_hip_fields_reserve_lattice.argtypes = [c_void_p, POINTER(c_size_t), c_size_t, c_int]
     lib.interpn_hip_fields_lattice_plan.argtypes = [c_size_t, c_int, c_size_t, POINTER(c_size_t), POINTER(c_size_t), c_size_t, c_int,
                                                     POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]
+    lib.interpn_hip_fields_eval_lattice_grad_device.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p,
+                                                                c_size_t, c_void_p, c_size_t, c_int, c_void_p, ctypes.c_uint,
+                                                                POINTER(c_int)]
+    lib.interpn_hip_fields_eval_lattice_grad_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p,
+                                                              c_size_t, c_void_p, c_size_t, c_int, POINTER(c_uint64)]
+    lib.interpn_hip_fields_reserve_lattice_grad.argtypes = lib.interpn_hip_fields_reserve_lattice.argtypes
+    lib.interpn_hip_fields_lattice_grad_plan.argtypes = lib.interpn_hip_fields_lattice_plan.argtypes
     lib.interpn_hip_eval_lattice_device.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p, c_void_p,
                                                     ctypes.c_uint, POINTER(c_int)]
     lib.interpn_hip_eval_lattice_host.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), c_size_t, c_void_p,

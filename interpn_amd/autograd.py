@@ -19,6 +19,10 @@ whose forward pass is one `Fields.eval_points_grad_tensors`; `pts.grad` has the 
 `Interpolator.eval_lattice_grad_tensors`; the backward pass sums the incoming `(*m)` gradient times component d over every
 lattice dimension but d, which gives one gradient per coordinate VECTOR.
 
+`interp_fields_lattice(fs, axes, field_axis=0)` is `interp_lattice` for a field set: a `(K, *m)` or `(*m, K)` tensor whose
+forward pass is one `Fields.eval_lattice_grad_tensors`; the backward pass sums the incoming gradient times `jac[f, d]` over
+the fields and over every lattice dimension but d.
+
 torch is imported on first use, and this module is not imported by `import interpn_amd`.
 """
 
@@ -29,6 +33,7 @@ _POINTS_FUNCTION = None
 _FIELDS_FUNCTION = None
 _FIELDS_POINTS_FUNCTION = None
 _LATTICE_FUNCTION = None
+_FIELDS_LATTICE_FUNCTION = None
 
 
 def _function():
@@ -219,3 +224,51 @@ def interp_lattice(it, axes):
     CUDA coordinate vectors of the handle's dtype): a tensor of shape `tuple(len(a) for a in axes)`, differentiable with
     respect to every vector of `axes`."""
     return _lattice_function().apply(it, *axes)
+
+
+def _fields_lattice_function():
+    """The field-set lattice torch.autograd.Function, built on first use like `_function`."""
+    global _FIELDS_LATTICE_FUNCTION
+    if _FIELDS_LATTICE_FUNCTION is not None:
+        return _FIELDS_LATTICE_FUNCTION
+    import torch
+
+    class _InterpFieldsLattice(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fs, field_axis, *axes):
+            flat = [a.detach().reshape(-1).contiguous() for a in axes]
+            out, jac = fs.eval_lattice_grad_tensors(flat, field_axis=field_axis)
+            fs.finish()
+            ctx.save_for_backward(jac)
+            ctx.axis_shapes = [a.shape for a in axes]
+            ctx.field_axis = field_axis
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            (jac,) = ctx.saved_tensors  # (K, N, *m), or (*m, K, N)
+            n = len(ctx.axis_shapes)
+            res = [None, None]
+            for d in range(n):
+                if not ctx.needs_input_grad[d + 2]:
+                    res.append(None)
+                    continue
+                # axes[d].grad[i] = sum over f and over every other lattice axis of grad_out * jac[f, d]
+                if ctx.field_axis == 0:
+                    full = grad_out * jac[:, d]
+                    dims = [0] + [1 + e for e in range(n) if e != d]
+                else:
+                    full = grad_out * jac[..., d]
+                    dims = [e for e in range(n) if e != d] + [n]
+                res.append(full.sum(dim=dims).reshape(ctx.axis_shapes[d]))
+            return tuple(res)
+
+    _FIELDS_LATTICE_FUNCTION = _InterpFieldsLattice
+    return _FIELDS_LATTICE_FUNCTION
+
+
+def interp_fields_lattice(fs, axes, field_axis: int = 0):
+    """Values of the field set `fs` (a multilinear or multicubic `Fields`) on the lattice axes[0] x .. x axes[N-1] (a sequence
+    of N torch CUDA coordinate vectors of the set's dtype): a tensor of shape `(K, *m)`, or `(*m, K)` with `field_axis=-1`,
+    differentiable with respect to every vector of `axes`.  The table stays a constant of the graph."""
+    return _fields_lattice_function().apply(fs, field_axis, *axes)

@@ -17,6 +17,8 @@
 //                     fields_reserve_points_grad)
 //   abi_fields_lattice.hip  field sets on a lattice (fields_eval_lattice_device / _host, fields_reserve_lattice, fields_lattice_plan)
 //   abi_lattice_grad.hip  value and gradient on a lattice (eval_lattice_grad_device / _host, lattice_grad_plan)
+//   abi_fields_lattice_grad.hip  values and Jacobian of a field set on a lattice (fields_eval_lattice_grad_device / _host,
+//                     fields_reserve_lattice_grad, fields_lattice_grad_plan)
 //   scratch_slots.h   (no HIP in it) scratch blocks between streams and stream marks: settle / take / release / reserve /
 //                     mark / the wait at destroy, against a runtime type; HipRuntime below is the product's
 //   abi_points.hip    point-major observation points (eval_points_device / _host, reserve_points) and their gradient form
@@ -433,6 +435,9 @@ size_t lattice_scratch_need(const GridDesc& g, const interpn::LatticeShape& s, c
 size_t lattice_reserve_need(const GridDesc& g, const interpn::LatticeShape& s);
 size_t lattice_expand_slice(const GridDesc& g, size_t npoints);
 int lattice_device(interpn_hip_interp* h, const interpn::LatticeShape& s, void* out, hipStream_t stream, unsigned flags, int* path_taken);
+// abi_lattice_grad.hip: the same with the gradient (`grad`: host array of ndims device pointers)
+int lattice_grad_device(interpn_hip_interp* h, const interpn::LatticeShape& s, void* out, void* const* grad, hipStream_t stream,
+                        unsigned flags, int* path_taken);
 constexpr size_t kExpandSliceBytes = (size_t)64 << 20;  // coordinates of one slice (bounds the scratch block)
 constexpr size_t kExpandSliceMin = (size_t)1 << 16;     // ... but never fewer points than this
 

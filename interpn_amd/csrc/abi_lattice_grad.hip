@@ -20,7 +20,12 @@ LatticePlan grad_plan_for(const GridDesc& g, const LatticeShape& s) {
   return lattice_grad_plan(g.method, g.ndims, g.dtype == kF64 ? 8 : 4, g.n, s.m, lattice_lds_budget(g.cfg), g.cfg.num_cus, g.cfg.lattice);
 }
 
-// One lattice on device arrays.  Arguments are validated; the current device is the handle's.
+}  // namespace
+
+namespace interpn_abi {
+
+// One lattice on device arrays.  Arguments are validated; the current device is the handle's.  (abi_internal.h: also the
+// per-field path of a field set, abi_fields_lattice_grad.hip.)
 int lattice_grad_device(interpn_hip_interp* h, const LatticeShape& s, void* out, void* const* grad, hipStream_t stream, unsigned flags,
                         int* path_taken) {
   const GridDesc& g = h->desc;
@@ -72,6 +77,10 @@ int lattice_grad_device(interpn_hip_interp* h, const LatticeShape& s, void* out,
   mark_stream(h, stream);
   return INTERPN_HIP_OK;
 }
+
+}  // namespace interpn_abi
+
+namespace {
 
 // validate_lattice's checks in their order, then the method, then the gradient arrays; *empty: nothing to do.
 int checks(const interpn_hip_interp* h, const void* const* axes, const size_t* axis_lens, size_t naxes, const void* out,

@@ -176,6 +176,51 @@ inline FieldsLatticePlan fields_lattice_plan(int method, int ndims, size_t elem,
   return p;
 }
 
+// ---- Field-set gradients on a lattice (lattice_fields_grad.h, k_lattice_fields_grad.hip) ---------------------------------
+// The product of the two kernels above: k_lattice_fields_rows' field loop, groups and fields-last tile around
+// k_lattice_grad_rows' L lines per field.  A wave owns G x L packed lines (field f of the group: lines f * L ..); per chunk
+// of 64 outputs a lane loads the last axis's record, width and sign once and computes, per field of the group, the value
+// and the N components.  Two result layouts (strides in elements):
+//   field-major   out[f * out_stride + p], jac[(f * N + d) * jac_stride + p]: N + 1 coalesced stores per field.
+//   fields-last   out[p * out_stride + f], jac[p * jac_stride + f * N + d]: the wave stages a [64] x P tile in LDS,
+//                 P = (G * (N + 1)) | 1 (a point's G values first, then its G x N Jacobian elements; the odd pitch keeps
+//                 the lanes of a column off one bank), and stores the values and then the Jacobian lane-contiguously.
+// LDS of a workgroup and the group size:
+//   wave_bytes(g) = round16(g * L * n_{N-1} * elem) + (fields-last ? round16(64 * ((g * (N + 1)) | 1) * elem) : 0)
+//   G             = the largest g in 1 .. min(K, kLatticeFieldsCap) with kLatticeWaves * wave_bytes(g) <= budget, 0 if none
+//   lds_bytes     = kLatticeWaves * wave_bytes(G)
+// At the default 20 KiB (5120 bytes per wave) a fields-last f64 3-D call never has G > 2: the tile of three fields is
+// 64 x 13 x 8 = 6656 bytes by itself, and the tile of two (4608) leaves room for lines of n_last <= 8 (multilinear) or 10
+// (multicubic) only, so G = 1 is the rule there.  The tile of N + 1 results per field takes the room; "axis_lds_kb" is the knob.
+inline size_t lattice_fields_grad_lines_bytes(int lines, size_t n_last, size_t elem, size_t g) {
+  return (g * (size_t)lines * n_last * elem + 15) & ~(size_t)15;
+}
+inline size_t lattice_fields_grad_tile_pitch(size_t g, int ndims) { return (g * (size_t)(ndims + 1)) | 1; }
+inline size_t lattice_fields_grad_wave_bytes(int lines, int ndims, size_t n_last, size_t elem, size_t g, int layout) {
+  const size_t tile = ((size_t)64 * lattice_fields_grad_tile_pitch(g, ndims) * elem + 15) & ~(size_t)15;
+  return lattice_fields_grad_lines_bytes(lines, n_last, elem, g) + (layout == kLatticeFieldsLast ? tile : 0);
+}
+
+// Which path a field set's value-and-Jacobian call takes on a lattice.  Fused when lattice_grad_plan says fused for the
+// mode (coverage, the `lattice` option, the two automatic rules) and a group of at least one field fits.  No rule of its
+// own: see DESIGN.md section 20 for what was and was not measured.
+inline FieldsLatticePlan fields_lattice_grad_plan(int method, int ndims, size_t elem, const int* n, const size_t* m, size_t nfields,
+                                                  int layout, size_t budget, int num_cus, int mode) {
+  FieldsLatticePlan p;
+  const LatticePlan one = lattice_grad_plan(method, ndims, elem, n, m, budget, num_cus, mode);
+  if (!one.fused || nfields == 0) return p;
+  const size_t n_last = (size_t)n[ndims - 1];
+  const int lines = lattice_grad_lines(method, ndims);
+  const size_t top = nfields < (size_t)kLatticeFieldsCap ? nfields : (size_t)kLatticeFieldsCap;
+  size_t g = 0;
+  while (g < top && (size_t)kLatticeWaves * lattice_fields_grad_wave_bytes(lines, ndims, n_last, elem, g + 1, layout) <= budget) ++g;
+  if (g == 0) return p;
+  p.fused = true;
+  p.group = g;
+  p.lds_bytes = (size_t)kLatticeWaves * lattice_fields_grad_wave_bytes(lines, ndims, n_last, elem, g, layout);
+  return p;
+}
+
 // The lattice as the kernels see it (host arrays of at most kMaxDims entries).
 struct LatticeShape {
   int ndims = 0;
@@ -211,5 +256,13 @@ hipError_t launch_lattice_fields_rows(const GridDesc& g, const LatticeShape& s, 
 // launch_lattice_axes; `lds_bytes` as lattice_grad_plan gives them.
 hipError_t launch_lattice_grad_rows(const GridDesc& g, const LatticeShape& s, const void* recs, void* out, void* const* grad,
                                     size_t lds_bytes, hipStream_t stream);
+
+// k_lattice_fields_grad.hip
+// The rows' values and Jacobian of `nfields` fields (field f at g.vals + f * field_stride elements) from the records of
+// launch_lattice_axes: groups of `group` fields, `lds_bytes` as fields_lattice_grad_plan gives them; `layout` and the two
+// strides as above.
+hipError_t launch_lattice_fields_grad_rows(const GridDesc& g, const LatticeShape& s, const void* recs, size_t field_stride,
+                                           size_t nfields, size_t group, void* out, size_t out_stride, void* jac, size_t jac_stride,
+                                           int layout, size_t lds_bytes, hipStream_t stream);
 
 }  // namespace interpn

@@ -4,7 +4,8 @@ channels, scipy's RegularGridInterpolator with trailing value dimensions.
 
 `Fields` is the persistent form (the counterpart of `Interpolator`), `interpn_fields()` the one-call
 form (the counterpart of `interpn()`), `interpn_fields_grad()` the one-call form with the Jacobian.  Row f of every result is bit-identical to what the single
-interpolator of field f returns.
+interpolator of field f returns.  On a lattice (one coordinate vector per axis): `Fields.eval_lattice*` /
+`interpn_fields_lattice()` for the values, `Fields.eval_lattice_grad*` / `interpn_fields_lattice_grad()` with the Jacobian.
 """
 
 from __future__ import annotations
@@ -55,6 +56,40 @@ def _lattice_out_stride(shape, strides, k, m, layout, contiguous) -> int:
     if shape != m + (k,):
         raise ValueError(f"out: expected shape {m + (k,)}, got {shape}")
     raise ValueError(f"out: expected a C-contiguous array, or a 2-D ({count}, >= {k}) view with contiguous rows")
+
+
+def _lattice_jac_stride(shape, strides, k, nd, m, layout, contiguous) -> int:
+    """`_lattice_out_stride` for the Jacobian of K fields in N dimensions on a lattice of axis lengths `m`: field-major
+    `(K, N, *m)` or `(K, N, prod(m))` with every (f, d) block contiguous and ONE stride between the K * N blocks;
+    fields-last `(*m, K, N)` C-contiguous, or a `(prod(m), K, N)` view whose rows of K * N elements are contiguous."""
+    count = int(np.prod(m, dtype=object)) if m else 0
+    shape, m = tuple(int(v) for v in shape), tuple(m)
+    if layout == _lib.FIELDS_LATTICE_FIELD_MAJOR:
+        if shape != (k, nd) + m and shape != (k, nd, count):
+            raise ValueError(f"jac: expected shape {(k, nd) + m}, got {shape}")
+        if count == 0:
+            return 0
+        want = 1  # each (f, d) block in C order
+        for n, st in zip(reversed(shape[2:]), reversed(strides[2:])):
+            if n > 1 and st != want:
+                raise ValueError("jac: each component's block must be contiguous")
+            want *= n
+        row = int(strides[1]) if nd > 1 else (int(strides[0]) if k > 1 else count)
+        if row < count or (k > 1 and nd > 1 and strides[0] != nd * row):
+            raise ValueError(f"jac: one uniform stride of at least {count} elements between the K * N blocks "
+                             "(stride(0) == N * stride(1))")
+        return row
+    if shape == m + (k, nd) and contiguous:
+        return k * nd
+    if len(shape) == 3 and shape == (count, k, nd):
+        if count and ((nd > 1 and strides[2] != 1) or (k > 1 and strides[1] != nd)):
+            raise ValueError("jac: every row of K * N elements must be contiguous")
+        if count > 1 and strides[0] < k * nd:
+            raise ValueError(f"jac: the row stride must be at least {k * nd} elements")
+        return int(strides[0]) if count > 1 else k * nd
+    if shape != m + (k, nd):
+        raise ValueError(f"jac: expected shape {m + (k, nd)}, got {shape}")
+    raise ValueError(f"jac: expected a C-contiguous array, or a 3-D ({count}, {k}, {nd}) view with contiguous rows")
 
 
 _ROWS_UNIT = "out: every row must be contiguous (unit stride along the last axis)"  # point-major (n, K) results
@@ -600,6 +635,97 @@ class Fields:
             raise TypeError(f"eval_lattice on host arrays takes no {extra}")
         return self.eval_lattice_host(axes, out, **kwargs)
 
+    # -- lattice values and Jacobian: (K, *m) values and (K, N, *m) Jacobian, or (*m, K) and (*m, K, N) ----
+    def reserve_lattice_grad(self, axis_lens, nstreams: int = 1) -> None:
+        """`reserve_lattice` for `eval_lattice_grad_*` (`interpn_hip_fields_reserve_lattice_grad`): the per-field slice holds
+        K (N + 1) rows.  The same limit of two concurrent streams for per-field evaluations with `field_axis=-1`."""
+        lens, n = _dims(axis_lens)
+        _lib.raise_for_status(_lib.load().interpn_hip_fields_reserve_lattice_grad(self._h, lens, n, int(nstreams)))
+
+    def _lattice_grad_shapes(self, m, field_axis):
+        k, nd = self.nfields, self._ndims
+        return ((k,) + m, (k, nd) + m) if field_axis == 0 else (m + (k,), m + (k, nd))
+
+    def eval_lattice_grad_host(self, axes, out=None, jac=None, field_axis: int = 0):
+        """Every field and its gradient on the lattice axes[0] x .. x axes[N-1] of host coordinate vectors (synchronous;
+        `interpn_hip_fields_eval_lattice_grad_host`): `(out, jac)` of shapes `(K, *m)` and `(K, N, *m)`, or `(*m, K)` and
+        `(*m, K, N)` with `field_axis=-1`.  `out` has the bits of `eval_lattice_host`; `jac[f, d]` (`jac[..., f, d]`) has
+        the bits of `Interpolator.eval_lattice_grad_host(axes)[1][d]` of field f alone.  `out` as for `eval_lattice_host`;
+        `jac`, field-major: every (f, d) block contiguous, one stride between the K N blocks; fields-last: C-contiguous, or
+        a `(prod(m), K, N)` view with contiguous rows.  On "Unrepresentable coordinate value" the AssertionError carries
+        `first_bad_index` (C order over m) and exactly the results in front of it are written, in both arrays."""
+        layout = _field_axis(field_axis)
+        aptr, alen, naxes, _keep = _slice_of_slices("axes", axes, self.dtype)
+        m = tuple(int(alen[i]) for i in range(naxes))
+        k, nd, item = self.nfields, self._ndims, self.dtype.itemsize
+        oshape, jshape = self._lattice_grad_shapes(m, field_axis)
+        if out is None:
+            out = np.zeros(oshape, dtype=self.dtype)
+        if jac is None:
+            jac = np.zeros(jshape, dtype=self.dtype)
+        _args.check_ndarray("out", out, self.dtype)
+        _args.check_ndarray("jac", jac, self.dtype)
+        if any(st % item for st in out.strides + jac.strides):
+            raise ValueError("out, jac: strides must be whole numbers of elements")
+        stride = _lattice_out_stride(out.shape, [st // item for st in out.strides], k, m, layout, out.flags.c_contiguous)
+        jstride = _lattice_jac_stride(jac.shape, [st // item for st in jac.strides], k, nd, m, layout, jac.flags.c_contiguous)
+        if not (out.flags.writeable and jac.flags.writeable):
+            raise ValueError("out, jac: array is read-only")
+        bad = c_uint64(0)
+        st = _lib.load().interpn_hip_fields_eval_lattice_grad_host(self._h, _args.void_pp(aptr), alen, naxes, c_void_p(out.ctypes.data),
+                                                                  stride, c_void_p(jac.ctypes.data), jstride, layout, ctypes.byref(bad))
+        _args.raise_for_indexed_status(st, bad)
+        return out, jac
+
+    def eval_lattice_grad_tensors(self, axes, out=None, jac=None, field_axis: int = 0, stream=None, no_alloc: bool = False):
+        """The same on torch CUDA tensors (asynchronous on torch's current stream unless given;
+        `interpn_hip_fields_eval_lattice_grad_device`): `axes` are contiguous 1-D tensors of the set's dtype; `out` and `jac`
+        must not overlap them or each other.  With `field_axis=-1` the kernel writes `(*m, K)` and `(*m, K, N)` itself: no
+        stack and no permuted copy behind K single-field calls.  `last_lattice_path` says which path ran; `finish()`
+        synchronises and raises for a coordinate the reference cannot evaluate."""
+        layout = _field_axis(field_axis)
+        want = _args.torch_dtype(self.dtype)
+        axes = list(axes)
+        dev = self.device() if self._h is not None and self._h.value else -1
+        _args.coord_tensors("axes", axes, want, dev, "set", same_length=False)
+        m = tuple(int(t.numel()) for t in axes)
+        k, nd = self.nfields, self._ndims
+        oshape, jshape = self._lattice_grad_shapes(m, field_axis)
+        if out is None or jac is None:
+            import torch
+
+            if out is None:
+                out = torch.empty(oshape, dtype=want, device=torch.device("cuda", dev))
+            if jac is None:
+                jac = torch.empty(jshape, dtype=want, device=torch.device("cuda", dev))
+        for name, a in (("out", out), ("jac", jac)):
+            if not (hasattr(a, "is_cuda") and a.is_cuda and a.dtype == want):
+                raise TypeError(f"{name}: expected a {want} CUDA tensor")
+            _args.same_device(name, a, dev, "set")
+        stride = _lattice_out_stride(out.shape, out.stride(), k, m, layout, out.is_contiguous())
+        jstride = _lattice_jac_stride(jac.shape, jac.stride(), k, nd, m, layout, jac.is_contiguous())
+        raw, owner = _args.resolve_stream(stream, dev)
+        n = len(axes)
+        lens = (ctypes.c_size_t * max(n, 1))(*m)
+        path = ctypes.c_int(0)
+        st = _lib.load().interpn_hip_fields_eval_lattice_grad_device(
+            self._h, _args.ptr_array(t.data_ptr() for t in axes), lens, n, c_void_p(out.data_ptr()), stride, c_void_p(jac.data_ptr()),
+            jstride, layout, c_void_p(int(raw)), _args.eval_flags(no_alloc), ctypes.byref(path))
+        _lib.raise_for_status(st)
+        self._pending_streams[raw] = owner
+        return out, jac
+
+    def eval_lattice_grad(self, axes, out=None, jac=None, **kwargs):
+        """`eval_lattice_grad_tensors` for torch tensors, `eval_lattice_grad_host` for numpy arrays (by the type of
+        `axes[0]`)."""
+        axes = list(axes)
+        if axes and _is_tensor(axes[0]):
+            return self.eval_lattice_grad_tensors(axes, out, jac, **kwargs)
+        extra = sorted(set(kwargs) - {"field_axis"})
+        if extra:
+            raise TypeError(f"eval_lattice_grad on host arrays takes no {extra}")
+        return self.eval_lattice_grad_host(axes, out, jac, **kwargs)
+
     def finish(self, stream=None) -> None:
         """Wait for the evaluations enqueued since the last finish; AssertionError("Unrepresentable coordinate
         value") with `.first_bad_index` if a point could not be evaluated (the same index for every field)."""
@@ -673,6 +799,53 @@ def interpn_fields_lattice(axes, grids, vals, *, method="linear", field_axis: in
             fs.finish()
         else:
             res = fs.eval_lattice_host(axes, out, field_axis=field_axis)
+    finally:
+        fs.close()
+    return res
+
+
+def fields_lattice_grad_plan(dtype, method: str, dims, axis_lens, nfields: int, field_axis: int = 0):
+    """`fields_lattice_plan` for a value-and-Jacobian call (`interpn_hip_fields_lattice_grad_plan`; needs no device): a
+    wave of the fused kernel keeps G x L lines (multilinear L = N + 1, multicubic L = N) and, for `field_axis=-1`, a tile of
+    (G (N + 1)) | 1 elements per point.  `method` "linear" or "cubic"."""
+    layout = _field_axis(field_axis)
+    d, nd = _dims(dims)
+    m, nm = _dims(axis_lens)
+    if nd != nm:
+        raise ValueError(f"axis_lens: expected {nd} lengths, got {nm}")
+    path, group, lds, npts = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    st = _lib.load().interpn_hip_fields_lattice_grad_plan(np.dtype(dtype).itemsize, _lib.METHODS[method], nd, d, m, int(nfields), layout,
+                                                          ctypes.byref(path), ctypes.byref(group), ctypes.byref(lds), ctypes.byref(npts))
+    _lib.raise_for_status(st)
+    return _lib.FIELDS_LATTICE_PATHS[path.value], int(group.value), int(lds.value), int(npts.value)
+
+
+def interpn_fields_lattice_grad(axes, grids, vals, *, method="linear", field_axis: int = 0, linearize_extrapolation: bool = True,
+                                assume_regular: bool = False):
+    """`interpn_fields_lattice()` with the Jacobian: every field and its derivative with respect to every coordinate on the
+    lattice axes[0] x .. x axes[N-1], one pass (`Fields.eval_lattice_grad`).  The rules are those of `interpn_fields_lattice`;
+    `method` is "linear" or "cubic" ("nearest" has no gradient: the library's "unsupported" error).
+
+    Returns `(val, jac)`.  `vals` (K, *dims): `val` (K, *m), `jac` (K, N, *m), `jac[f, d]` the derivative of field f with
+    respect to coordinate d, with the bits of `interpn_lattice_grad` of field f.  With `field_axis=-1` the channel-last
+    layout, written by the kernel: `vals` (*dims, K), `val` (*m, K), `jac` (*m, K, N) — the Jacobian of a displacement field
+    on a finer mesh, the per-channel gradients of a resized image."""
+    _field_axis(field_axis)
+    _setup.check_method(method)
+    axes = list(axes)
+    dtype, grids, k, nper = _setup.grids_and_fields(grids, vals, field_axis, naxes=len(axes))
+    on_device = bool(axes) and _setup.is_cuda_tensor(axes[0])
+    device = _setup.device_index(axes[0]) if on_device else -1
+    axes = _setup.flat_coords(axes, on_device)
+    vals = _setup.field_major(vals, k, nper, field_axis == -1, on_device)
+    fs = _setup.create(Fields, method, grids, _setup.regular_spec(grids, dtype, assume_regular), vals, dtype, device,
+                       linearize_extrapolation=linearize_extrapolation)
+    try:
+        if on_device:
+            res = fs.eval_lattice_grad_tensors(axes, field_axis=field_axis)
+            fs.finish()
+        else:
+            res = fs.eval_lattice_grad_host(axes, field_axis=field_axis)
     finally:
         fs.close()
     return res
